@@ -9,7 +9,12 @@ HBM-resident corpus: trainer creation (symbol widening, word boundaries, the
 initial pair count) plus all 32,512 merges (every 128-merge host round trip of
 trainer.js:225-335).  `value` = merges of the K timed runs / their wall time.
 
-Secondary legs (same JSON line):
+A plain run (`--gpus 1 --steps K --warmup W`) generates the corpus, runs W
+untimed and K timed steps and prints the headline's JSON line; `--dump-outputs
+DIR` also writes the last timed step's merge list to DIR/merges.npy.  Everything
+below is measured or checked only with `--full`.
+
+Secondary legs (--full, same JSON line):
   * c1: BASELINE configs[0] (1K vocab on 256 KiB ASCII, seed 1), full runs, with
     the full 768-merge CPU run on 1 core and on the CPU share beside it;
   * c2: BASELINE configs[1] (100 MiB English, seed 2, 32K vocab), full runs;
@@ -401,9 +406,13 @@ def headline_leg(args, lib, ctx, dist):
     log(f"[bench] headline corpus {len(data)} B generated in {time.time() - t:.1f}s")
     d = device_buffer(lib, ctx, data)
     n = len(data)
-    pairs = []
+    pairs = [] if args.full else None
     wall, total, last, st = timed_runs(args, lib, ctx, dist, d, n, args.vocab, args.steps, args.warmup,
                                        pairs_out=pairs)
+    if not args.full:   # a plain run: the timed steps are all the headline figure needs
+        lib.gbpe_device_free(ctx, d)
+        det = {"bytes_per_symbol": int(st.bytes_per_symbol), "merges_per_run": int(last.shape[0])}
+        return data, wall, total, last, det, {}
     sk = None
     if not args.no_kernel_timing:
         from gpubpe import _lib
@@ -690,11 +699,13 @@ def single_line(args, lib, ctx, dist, rank):
                                "corpus",
                    "train_bytes": HEADLINE["n"], "target_vocab": args.vocab,
                    "merges_per_step": det["merges_per_run"], "parallelism": "single"},
-        "roofline": train_roofline(det, wall / max(1, args.steps)),
-        "reference_rate": det["reference_rate"],
-        "train_detail": det,
-        "parity": parity,
     }
+    if not args.full:
+        return line, last
+    line["roofline"] = train_roofline(det, wall / max(1, args.steps))
+    line["reference_rate"] = det["reference_rate"]
+    line["train_detail"] = det
+    line["parity"] = parity
     if not args.no_c1:
         line["c1"] = c1_leg(args, lib, ctx, dist)
     if not args.no_c2:
@@ -736,7 +747,7 @@ def single_line(args, lib, ctx, dist, rank):
         line["parity"]["train_cpu_first_merges_equal"] = cpu_merges == last[: len(cpu_merges)].tolist()
         if enc_base is not None:
             line["tokenize"]["cpu_baseline"] = enc_base
-    return line
+    return line, last
 
 
 # ── multi-GPU: strong scaling over one corpus ──────────────────────────────────
@@ -945,6 +956,29 @@ def lexshard_line(args, lib, ctx, dist, rank, world):
     wall = dist.max(t1 - t0)
     timing = lex_timing(dist, tr)
     lib.gbpe_device_free(ctx, d)
+    line = {
+        "metric": METRIC,
+        "value": round(total / wall, 1),
+        "unit": "merges/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(1e3 * wall / max(1, args.steps), 3),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "u16" if args.vocab <= 32768 else "u32",
+        "data": "synthetic (seeded Zipf English-like corpus, gpubpe.synth)",
+        "config": {"workload": f"headline: 32K-vocab BPE train on one 1,073,741,824 B English-like UTF-8 corpus "
+                               f"(seed 2) cut at word starts into {world} pieces; step = one complete training run: "
+                               "per-rank first pass (symbols, word boundaries, pair counts, word lexicon) on every "
+                               "GPU, stores to the last rank, one global lexicon, all 32,512 merges there (the merge "
+                               "chain is sequential), merge list broadcast",
+                   "train_bytes": HEADLINE["n"], "target_vocab": args.vocab,
+                   "merges_per_step": int(last.shape[0]), "parallelism": f"lexshard{world} ({dist.transport})"},
+    }
+    if not args.full:
+        return line, last
     want, meta = fixture("en1g")
     parity = {}
     if want is not None and args.vocab == 32768:
@@ -967,38 +1001,17 @@ def lexshard_line(args, lib, ctx, dist, rank, world):
         if not args.no_cpu:
             cpu_base, _, _ = cpu_baselines(args, full, None)
     dist.barrier()
-    line = {
-        "metric": METRIC,
-        "value": round(total / wall, 1),
-        "unit": "merges/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(1e3 * wall / max(1, args.steps), 3),
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "u16" if args.vocab <= 32768 else "u32",
-        "data": "synthetic (seeded Zipf English-like corpus, gpubpe.synth)",
-        "config": {"workload": f"headline: 32K-vocab BPE train on one 1,073,741,824 B English-like UTF-8 corpus "
-                               f"(seed 2) cut at word starts into {world} pieces; step = one complete training run: "
-                               "per-rank first pass (symbols, word boundaries, pair counts, word lexicon) on every "
-                               "GPU, stores to the last rank, one global lexicon, all 32,512 merges there (the merge "
-                               "chain is sequential), merge list broadcast",
-                   "train_bytes": HEADLINE["n"], "target_vocab": args.vocab,
-                   "merges_per_step": int(last.shape[0]), "parallelism": f"lexshard{world} ({dist.transport})"},
-        "roofline": roof,
-        "train_detail": {"timing_s_max_over_ranks": timing,
-                         "pieces": {"symbols": sh[:, 5].tolist(), "store_symbols": sh[:, 0].tolist(),
-                                    "entries": sh[:, 1].tolist(), "words": sh[:, 2].tolist(),
-                                    "zone": int(sh[-1, 4])},
-                         "amdahl": "only the first pass runs on every GPU; the merge loop (~90 % of a single-GPU "
-                                   "run at 1 GiB) stays on one: DESIGN §5"},
-        "replicated": {"value": round(rtotal / rwall, 1), "unit": "merges/s", "runs": 2,
-                       "meaning": "every rank trains the whole corpus on its own GPU (no exchange); max wall",
-                       "merges_equal_fixture": bool(want is not None and np.array_equal(rlast, want))},
-        "parity": parity,
-    }
+    line["roofline"] = roof
+    line["train_detail"] = {"timing_s_max_over_ranks": timing,
+                            "pieces": {"symbols": sh[:, 5].tolist(), "store_symbols": sh[:, 0].tolist(),
+                                       "entries": sh[:, 1].tolist(), "words": sh[:, 2].tolist(),
+                                       "zone": int(sh[-1, 4])},
+                            "amdahl": "only the first pass runs on every GPU; the merge loop (~90 % of a single-GPU "
+                                      "run at 1 GiB) stays on one: DESIGN §5"}
+    line["replicated"] = {"value": round(rtotal / rwall, 1), "unit": "merges/s", "runs": 2,
+                          "meaning": "every rank trains the whole corpus on its own GPU (no exchange); max wall",
+                          "merges_equal_fixture": bool(want is not None and np.array_equal(rlast, want))}
+    line["parity"] = parity
     if cpu_base is not None:
         line["cpu_baseline"] = cpu_base
     if rst is not None:
@@ -1006,7 +1019,7 @@ def lexshard_line(args, lib, ctx, dist, rank, world):
                                         "lexicon_entries": int(rst.lexicon_entries)}
     if not args.no_encode:
         line["tokenize"] = split_encode_leg(args, lib, ctx, dist, rank, world)
-    return line
+    return line, last
 
 
 C4_SHARD = 1 << 30   # 8 x 1 GiB multilingual, seed 5 + rank, 64K vocab
@@ -1096,15 +1109,24 @@ def replicated_line(args, lib, ctx, dist, rank, world):
                                "merges / max wall over ranks",
                    "train_bytes": HEADLINE["n"], "target_vocab": args.vocab,
                    "merges_per_step": det["merges_per_run"], "parallelism": f"replicated{world}"},
-        "roofline": train_roofline(det, wall / max(1, args.steps)),
-        "train_detail": det,
-        "parity": parity,
     }
+    if not args.full:
+        return line, last
+    line["roofline"] = train_roofline(det, wall / max(1, args.steps))
+    line["train_detail"] = det
+    line["parity"] = parity
     ok = 1.0 if parity.get("train_merges_equal_fixture", True) else 0.0
     line["parity"]["all_ranks_merges_equal_fixture"] = -dist.max(-ok) == 1.0
     if not args.no_encode:
         line["tokenize"] = split_encode_leg(args, lib, ctx, dist, rank, world)
-    return line
+    return line, last
+
+
+def dump_outputs(path: str, merges: np.ndarray):
+    """What the last timed step returned to its caller: the merge list, one row
+    (left id, right id, new id, pair count) per merge; u32 values are exact in float64."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "merges.npy"), merges.astype(np.float64))
 
 
 def main():
@@ -1112,6 +1134,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5, help="timed steps: complete training runs of the headline corpus")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every secondary leg, check and roofline (the --no-* options "
+                         "pick among them); without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's merge list to DIR/merges.npy (float64 [merges, 4])")
     ap.add_argument("--vocab", type=int, default=32768)
     ap.add_argument("--encode-bytes", type=int, default=1 << 30)
     ap.add_argument("--vocab-sample-bytes", type=int, default=104_857_600)
@@ -1142,19 +1169,22 @@ def main():
     rc = lib.gbpe_ctx_create(int(os.environ.get("GBPE_BENCH_DEVICE", local)) if world > 1 else 0, C.byref(ctx))
     if rc != 0:
         raise SystemExit(f"gbpe_ctx_create failed ({rc}): no MI355X visible")
+    last = None
     if args.c4_only:
         line = {"metric": METRIC, "c4": c4_line(args, lib, ctx, dist, rank, world)}
     elif world > 1 and args.replicated:
-        line = replicated_line(args, lib, ctx, dist, rank, world)
+        line, last = replicated_line(args, lib, ctx, dist, rank, world)
     elif world > 1:
-        line = lexshard_line(args, lib, ctx, dist, rank, world)
-        if world == 8 and not args.no_c4:   # C4's configuration: one 1 GiB shard per GPU
+        line, last = lexshard_line(args, lib, ctx, dist, rank, world)
+        if args.full and world == 8 and not args.no_c4:   # C4's configuration: one 1 GiB shard per GPU
             try:
                 line["c4"] = c4_line(args, lib, ctx, dist, rank, world)
             except Exception as e:  # noqa: BLE001
                 line["c4"] = {"error": f"{type(e).__name__}: {e}"}
     else:
-        line = single_line(args, lib, ctx, dist, rank)
+        line, last = single_line(args, lib, ctx, dist, rank)
+    if rank == 0 and args.dump_outputs and last is not None:
+        dump_outputs(args.dump_outputs, last)
     if rank == 0:
         print(json.dumps(line), flush=True)
     lib.gbpe_ctx_destroy(ctx)

@@ -17,6 +17,9 @@ Generation is vectorised (piece table + gather) so 1 GiB takes seconds.
 """
 from __future__ import annotations
 
+import os
+from concurrent.futures import ThreadPoolExecutor
+
 import numpy as np
 
 _EN_LETTERS = "etaoinshrdlcumwfgypbvkjxqz"
@@ -71,12 +74,18 @@ def _script_lexicons(seed: int = 2000, n: int = 5000) -> dict:
     }
 
 
-def _assemble(pieces: list[bytes], ids: np.ndarray) -> np.ndarray:
-    """Concatenate pieces[ids] into one uint8 array (vectorised gather)."""
+def _piece_table(pieces: list[bytes]):
+    """(flat bytes, start of every piece in them, length of every piece)."""
     lens = np.array([len(p) for p in pieces], dtype=np.int64)
     flat = np.frombuffer(b"".join(pieces), dtype=np.uint8)
     starts = np.zeros(len(pieces), dtype=np.int64)
     starts[1:] = np.cumsum(lens)[:-1]
+    return flat, starts, lens
+
+
+def _gather(table, ids: np.ndarray) -> np.ndarray:
+    """Concatenate the table's pieces[ids] into one uint8 array (vectorised gather)."""
+    flat, starts, lens = table
     L = lens[ids]
     total = int(L.sum())
     out_off = np.zeros(len(ids), dtype=np.int64)
@@ -85,38 +94,74 @@ def _assemble(pieces: list[bytes], ids: np.ndarray) -> np.ndarray:
     return flat[src]
 
 
+def _assemble(pieces: list[bytes], ids: np.ndarray) -> np.ndarray:
+    """Concatenate pieces[ids] into one uint8 array."""
+    return _gather(_piece_table(pieces), ids)
+
+
+def _threads() -> int:
+    return int(os.environ.get("OMP_NUM_THREADS", "0")) or min(16, os.cpu_count() or 1)
+
+
+def _put(out: np.ndarray, at: int, table, ids: np.ndarray) -> None:
+    chunk = _gather(table, ids)
+    out[at:at + chunk.shape[0]] = chunk[:out.shape[0] - at]
+
+
 def _word_stream(rng, lex: list[bytes], n_bytes: int, fancy_punct: float, space_sep: bool = True) -> np.ndarray:
-    """Words (Zipf 1.1) + separators until ``n_bytes`` are produced."""
+    """Words (Zipf 1.1) + separators until ``n_bytes`` are produced.
+
+    The generator's draws stay on the calling thread, in a fixed order (they
+    define the corpus); the word lookup and the byte gather of every block of
+    words run on a thread pool, slice by slice, straight into the output."""
     V = len(lex)
     p = _zipf_p(V)
+    # rng.choice(V, size=W, p=p) is rng.random(W) looked up in p's normalised
+    # cumulative sum (numpy Generator.choice); the lookup is the slow half, so it
+    # is done here per slice (tests/test_synth.py holds the two equal)
+    cdf = p.cumsum()
+    cdf /= cdf[-1]
     sp = b" " if space_sep else b""
     seps = [sp, b"," + sp, b"." + sp, b"\n", b",\n", b".\n",
             "’".encode() + sp, " “".encode(), "”".encode() + sp, " —".encode() + sp]
-    pieces = list(lex) + seps
+    table = _piece_table(list(lex) + seps)
+    lens = table[2]
     avg = float(np.dot(p, [len(w) for w in lex])) + 1.0
-    out, have = [], 0
-    while have < n_bytes:
-        W = int(min(8_000_000, max(1024, (n_bytes - have) / avg * 1.05)))
-        words = rng.choice(V, size=W, p=p)
-        # newline after every 8-16 words
-        gaps = rng.integers(8, 17, size=W // 8 + 2)
-        nl_pos = np.cumsum(gaps)
-        nl_pos = nl_pos[nl_pos < W]
-        is_nl = np.zeros(W, dtype=bool)
-        is_nl[nl_pos] = True
-        u = rng.random(W)
-        punct = np.where(u < 0.05, 1, np.where(u < 0.10, 2, 0))          # ',' / '.' p = 0.05 each
-        sep = np.where(is_nl, 3 + punct, punct)
-        if fancy_punct > 0:
-            f = rng.random(W) < fancy_punct
-            sep = np.where(f & ~is_nl, 6 + rng.integers(0, 4, size=W), sep)
-        ids = np.empty(2 * W, dtype=np.int64)
-        ids[0::2] = words
-        ids[1::2] = V + sep
-        chunk = _assemble(pieces, ids)
-        out.append(chunk)
-        have += chunk.shape[0]
-    return np.concatenate(out)[:n_bytes]
+    out, have, puts = np.empty(n_bytes, dtype=np.uint8), 0, []
+    T = _threads()
+    with ThreadPoolExecutor(T) as pool:
+        while have < n_bytes:
+            W = int(min(8_000_000, max(1024, (n_bytes - have) / avg * 1.05)))
+            uw = rng.random(W)
+            # newline after every 8-16 words
+            gaps = rng.integers(8, 17, size=W // 8 + 2)
+            nl_pos = np.cumsum(gaps)
+            nl_pos = nl_pos[nl_pos < W]
+            is_nl = np.zeros(W, dtype=bool)
+            is_nl[nl_pos] = True
+            u = rng.random(W)
+            if fancy_punct > 0:
+                uf, fancy = rng.random(W), rng.integers(0, 4, size=W)
+
+            def ids_of(a, b):
+                words = cdf.searchsorted(uw[a:b], side="right")
+                punct = np.where(u[a:b] < 0.05, 1, np.where(u[a:b] < 0.10, 2, 0))    # ',' / '.' p = 0.05 each
+                sep = np.where(is_nl[a:b], 3 + punct, punct)
+                if fancy_punct > 0:
+                    sep = np.where((uf[a:b] < fancy_punct) & ~is_nl[a:b], 6 + fancy[a:b], sep)
+                ids = np.empty(2 * (b - a), dtype=np.int64)
+                ids[0::2] = words
+                ids[1::2] = V + sep
+                return ids, int(lens[ids].sum())
+
+            cuts = np.linspace(0, W, max(1, min(T, W >> 16)) + 1).astype(np.int64).tolist()
+            for ids, nb in list(pool.map(ids_of, cuts[:-1], cuts[1:])):
+                if have < n_bytes:
+                    puts.append(pool.submit(_put, out, have, table, ids))
+                have += nb
+        for f in puts:
+            f.result()
+    return out
 
 
 def english(n_bytes: int, seed: int = 1, fancy_punct: float = 0.0) -> bytes:

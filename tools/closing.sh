@@ -1,4 +1,4 @@
-# Final checks of the round (one GPU call): the whole -m gpu suite, smoke(), the default bench
+# Final checks of the round (one GPU call): the whole -m gpu suite, smoke(), the bench with every leg
 set -o pipefail
 export TMPDIR=/tmp
 O=gpurun_out/closing
@@ -7,7 +7,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout
 tail -1 $O/gpu_tests.txt
 timeout -k 10 240 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 || { echo SMOKEFAIL; tail -20 $O/smoke.txt; exit 1; }
 tail -1 $O/smoke.txt
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err || { echo BENCHFAIL; tail -20 $O/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err || { echo BENCHFAIL; tail -20 $O/bench.err; exit 1; }
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/closing/bench.json").read().strip().splitlines()[-1])

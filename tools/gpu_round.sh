@@ -4,7 +4,7 @@
 # STEP:
 #   tests[=EXPR]        pytest -m gpu (-k EXPR)                 -> OUT/gpu_tests.txt
 #   smoke               __graft_entry__.smoke()                 -> OUT/smoke.txt
-#   bench[=ARGS]        python bench.py ARGS                     -> OUT/bench.json
+#   bench[=ARGS]        python bench.py ARGS (--full: every leg)  -> OUT/bench.json
 #   'ab=LIBS -- NAMES'  tools/ab_libs.py LIBS -- NAMES (LIBS ' '-, NAMES ','-separated; AB_REPS / AB_ROUNDS
 #                       from the environment)                    -> OUT/ab.txt
 #   stats=ARGS          rocprofv3 --kernel-trace --stats over bench.py ARGS -> OUT/prof

@@ -1,5 +1,5 @@
 """HBM traffic per k_body launch from two rocprofv3 --pmc passes of
-`bench.py --no-encode --no-cpu --no-kernel-timing` (FETCH_SIZE and WRITE_SIZE
+`bench.py --full --no-encode --no-cpu --no-kernel-timing` (FETCH_SIZE and WRITE_SIZE
 collected separately, MI355X_MICROARCH.md §HBM), next to the bytes k_body
 itself counts (train_detail.body_bytes_run of the same command's JSON line).
 
