@@ -758,6 +758,8 @@ struct SelShard {
     uint32_t zf = 3;         // zone rule: z >= max(2 mc + mc_prev, zf mc) + 2 (trainer zone_f)
     uint32_t sub = 1;        // k_body workgroups per bitmap word (1, 2, 4: a row of few words, body_grid)
     uint32_t k2 = 0;         // paired launches allowed (the zone_one form: zone_two)
+    uint32_t prej = 0;       // tests (GBPE_DEBUG prej): zone_two's verdict also rejects candidate c when
+                             // c % prej == prej - 1 (0: off; reference compaction only)
 };
 
 // The second merge of a paired launch.  With P1 > P2 the table's two
@@ -937,7 +939,8 @@ template <typename S, bool EXACT, int BT, int NT, int ZPT>
 __device__ __forceinline__ void zone_two(DevState* st, DevState* zst, const DevState& gs, uint32_t z, S* __restrict__ zc,
                                          S* __restrict__ zo, ZSegState* zg, ZoneLds<S, BT>& L, S* __restrict__ wb2,
                                          LdsTab<NT>& ltab, const Table& tb, uint32_t a, uint32_t b, uint32_t nw,
-                                         uint32_t mc, const Sel2& s2, uint64_t* __restrict__ bytes, uint32_t round) {
+                                         uint32_t mc, const Sel2& s2, uint64_t* __restrict__ bytes, uint32_t round,
+                                         uint32_t prej) {
     (void)round;   // phase stamps only (-DGBPE_KTRACE: 2 loaded, 3 merge-1 deltas, 7 merge 1 in LDS, 8 verdict,
                    // 9 merge 2 in LDS, 4 stored; the caller stamps 5 after the flush)
     constexpr uint32_t WS = Sym<S>::WS, TM = Sym<S>::TM;
@@ -1177,10 +1180,13 @@ __device__ __forceinline__ void zone_two(DevState* st, DevState* zst, const DevS
             const uint64_t c2 = (uint64_t)cnt + d;
             if (c2 > mc2 || (c2 == mc2 && vq[k] < pid2)) rej = true;
         }
+        // tests (GBPE_DEBUG prej): every prej-th candidate is turned down after the verdict above ran
+        // (gs: the launch's snapshot of the state; only this workgroup counts candidates)
+        if (t == 0 && prej && gs.pair_cand % prej == prej - 1u) rej = true;
         rej = __syncthreads_or(rej) != 0;
     }
     if (t == 0) {
-        st->pair_cand += 1u;   // (diagnostics: one zone workgroup per launch)
+        st->pair_cand += 1u;   // (the stats' pair_candidates / pair_rejected: one zone workgroup per launch)
         if (rej) st->pair_rej += 1u;
         if (!rej) {   // commit P2: every occurrence is a site of the second merge
             const uint32_t idx = (uint32_t)h2 == pid2 ? h2i : table_find(tb, pid2);
@@ -1470,7 +1476,8 @@ __global__ __launch_bounds__(BT) void k_body(DevState* st, uint32_t round, S* __
             if constexpr (PAIR && !ZP_OFF) {
                 if (s2.dbl) {
                     zone_two<S, EXACT, BT, zp_lt<S>(), ZPT>(st, zst, *gs, zs->n, zcur, zoth, zg, u.zw.z, u.zw.wb2,
-                                                            u.zw.lt, xtb, a, b, nw, mc, s2, wg_bytes + nbody, round);
+                                                            u.zw.lt, xtb, a, b, nw, mc, s2, wg_bytes + nbody, round,
+                                                            shx.prej);
                     two = true;
                 }
             }

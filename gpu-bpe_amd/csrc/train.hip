@@ -601,6 +601,8 @@ extern "C" int gbpe_trainer_stats_get(gbpe_trainer* t, gbpe_trainer_stats* o) {
     o->ms_body = t->ms_body;
     o->ms_create = t->ms_create;
     o->paired_merges = t->pair_done;
+    o->pair_candidates = t->h_st->pair_cand;
+    o->pair_rejected = t->h_st->pair_rej;
     o->zone_bytes = t->h_st->sp_bytes;
     o->lexicon_builds = (uint32_t)t->lx_builds;
     o->lexicon_fallbacks = (uint32_t)t->lx_fallbacks;

@@ -125,6 +125,7 @@ struct gbpe_trainer {
     bool pair_one = true;        // zones just above the zone_one form shrink into it (GBPE_DEBUG pone)
     double pair_rate = 0.5;      // second merges per launch of the last paired step (sizes the next step's launches)
     uint64_t pair_done = 0;      // merges run as the second of a launch (stats)
+    uint32_t pair_prej = 0;      // GBPE_DEBUG prej=k (tests): the verdict rejects every k-th candidate (0: off)
     uint32_t ptrace = 0;         // GBPE_DEBUG ptrace=1: every step's form and pairing on stderr
     uint32_t* d_clog = nullptr;  // GBPE_SPARSE_TRACE: per-merge candidate / hit sectors
     uint32_t* h_clog = nullptr;
@@ -447,6 +448,7 @@ int launch_merge_sparse(gbpe_trainer* t, uint32_t round, hipStream_t s, const Sp
     SelShard sh = sel_single(t);
     sh.sub = g.sub;
     sh.k2 = g.pair ? 1u : 0u;
+    sh.prej = t->pair_prej;
     if ((uint64_t)g.body + 1 > t->wg_cap)   // k_body's per-workgroup byte counters (and the zone's after them)
         return gbpe_set_error(t->ctx, GBPE_E_INTERNAL, "k_body grid (%u) above its byte counters (%llu)", g.body,
                               (unsigned long long)t->wg_cap);
@@ -1403,6 +1405,7 @@ void trainer_config(gbpe_trainer* t, gbpe_ctx* ctx, const gbpe_train_opts* opts)
     t->body_fit = gbpe_debug_knob("bodyfit", 1) != 0;
     t->pair_on = gbpe_debug_knob("pair", 1) != 0;
     t->pair_one = gbpe_debug_knob("pone", 1) != 0;
+    t->pair_prej = (uint32_t)std::max<long>(0, gbpe_debug_knob("prej", 0));
     t->ptrace = (uint32_t)gbpe_debug_knob("ptrace", 0);
     t->rehash_on = gbpe_debug_knob("rehash", 1) != 0;
     t->delta_mt = (uint32_t)gbpe_debug_knob("delta_mt", t->delta_mt);

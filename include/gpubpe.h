@@ -28,8 +28,9 @@
 extern "C" {
 #endif
 
-#define GBPE_ABI_VERSION 5   /* 5: paired_merges added to the stats, gbpe_ctx_trim (round 6); 4: the late-loop
-                                 stats removed, trainer creation time added (round 5) */
+#define GBPE_ABI_VERSION 6   /* 6: pair_candidates, pair_rejected added at the end of the stats; 5: paired_merges
+                                 added to the stats, gbpe_ctx_trim (round 6); 4: the late-loop stats removed,
+                                 trainer creation time added (round 5) */
 
 /* status codes */
 #define GBPE_OK            0
@@ -187,6 +188,9 @@ typedef struct gbpe_trainer_stats {
     double   ms_create;           /* host wall ms of trainer creation (symbols, word starts, first count):
                                      the part of a run the reference's t_loop excludes (trainer.js:230) */
     uint64_t paired_merges;       /* merges run as the second merge of a paired k_body launch */
+    uint64_t pair_candidates;     /* launches whose top two pairs allowed a second merge */
+    uint64_t pair_rejected;       /* ... whose second merge the zone workgroup's verdict turned down (reference
+                                     compaction only; pair_candidates - pair_rejected == paired_merges) */
 } gbpe_trainer_stats;
 int gbpe_trainer_stats_get(gbpe_trainer* t, gbpe_trainer_stats* out);
 /* Current symbol stream in the reference u32 layout (bit16 = word start). */

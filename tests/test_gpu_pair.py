@@ -8,12 +8,15 @@ so the late (zone_one) form, where launches pair, runs from the first steps, and
 check every merge [a, b, id, count], the final stream and the live pair counts in
 both compaction modes, on corpora with same-symbol runs (a == b), count ties, token
 0 and external word starts; and that the pairing itself happened (paired_merges),
-and that GBPE_DEBUG=pair=0 (one merge per launch) gives the same results.
+and that GBPE_DEBUG=pair=0 (one merge per launch) gives the same results.  Every
+run's counters must add up: each candidate launch either ran its second merge or
+was rejected (test_gpu_pair_reject.py checks the rejected path itself).
 """
 import numpy as np
 import pytest
 
 import bpe_oracle as O
+from pair_corpora import random_case
 from test_gpu_parity import _train_native, _assert_counts_match_stream
 
 pytestmark = pytest.mark.gpu
@@ -23,6 +26,14 @@ pytestmark = pytest.mark.gpu
 def eng():
     from gpubpe import BPEEngine
     return BPEEngine(0).init()
+
+
+def _assert_pair_counters(st, exact=False):
+    """Every candidate launch ran its second merge or was rejected; the exact compaction has no verdict."""
+    assert st.pair_candidates - st.pair_rejected == st.paired_merges, (st.pair_candidates, st.pair_rejected,
+                                                                       st.paired_merges)
+    if exact:
+        assert st.pair_rejected == 0
 
 
 def _corpus(kind):
@@ -55,6 +66,7 @@ def test_paired_launches_match_oracle(eng, kind, target, batch, exact):
     assert m == ref["merges"]
     assert np.array_equal(s, ref["symbols"])
     _assert_counts_match_stream(pairs, s)
+    _assert_pair_counters(st, exact)
     if not exact:
         assert st.tail_dropped == sum(ref["tail_drops"])
     if kind == "english":
@@ -71,12 +83,14 @@ def test_paired_external_word_starts_and_u32(eng):
         m, s, pairs, st = _train_native(eng, code, 1000, word_starts=ws, exact=exact, batch=32, sparse="early")
         assert m == ref["merges"] and np.array_equal(s, ref["symbols"])
         _assert_counts_match_stream(pairs, s)
+        _assert_pair_counters(st, exact)
     data = synth.english(60000, seed=23)   # a 40K vocab: u32 symbols
     ref = O.train(data, 40000)
     m, s, pairs, st = _train_native(eng, data, 40000, batch=64, sparse="early")
     assert st.bytes_per_symbol == 4
     assert m == ref["merges"] and np.array_equal(s, ref["symbols"])
     _assert_counts_match_stream(pairs, s)
+    _assert_pair_counters(st)
 
 
 def test_pairing_off_gives_the_same_run(eng, monkeypatch):
@@ -86,6 +100,8 @@ def test_pairing_off_gives_the_same_run(eng, monkeypatch):
     monkeypatch.setenv("GBPE_DEBUG", "pair=0")
     off = _train_native(eng, data, 1500, batch=128, sparse="early")
     assert on[3].paired_merges > 0 and off[3].paired_merges == 0
+    _assert_pair_counters(on[3])
+    assert off[3].pair_candidates == 0 and off[3].pair_rejected == 0
     assert on[0] == off[0] and np.array_equal(on[1], off[1])
     assert on[3].tail_dropped == off[3].tail_dropped
 
@@ -97,25 +113,13 @@ def test_paired_random_corpora(eng):
     final stream and every live pair count equal the oracle's, and pairing happens."""
     paired = 0
     for seed in range(8):
-        rng = np.random.default_rng(1000 + seed)
-        alpha = rng.choice(list(b"abcdefghijklmnop"), size=int(rng.integers(2, 8)), replace=False)
-        nv = int(rng.integers(300, 2000))
-        vocab = [bytes(rng.choice(alpha, size=int(n)).tolist()) for n in rng.integers(1, 9, size=nv)]
-        p = 1.0 / np.arange(1, nv + 1) ** rng.uniform(0.8, 1.3)
-        words = rng.choice(nv, size=int(rng.integers(12000, 24000)), p=p / p.sum())
-        data = bytearray(b" ".join(vocab[i] for i in words))
-        if seed % 3 == 0:   # token 0 never pairs (train.wgsl:395-399)
-            for i in rng.integers(0, len(data), len(data) // 200):
-                data[i] = 0
-        data = bytes(data)
-        exact = bool(seed & 1)
-        target = 256 + int(rng.integers(300, 1200))
-        batch = int(rng.choice([16, 64, 128]))
+        data, exact, target, batch = random_case(seed)
         ref = O.train(data, target, compaction="exact" if exact else "reference")
         m, s, pairs, st = _train_native(eng, data, target, exact=exact, batch=batch, sparse="early")
         assert m == ref["merges"], f"seed {seed}"
         assert np.array_equal(s, ref["symbols"]), f"seed {seed}"
         _assert_counts_match_stream(pairs, s)
+        _assert_pair_counters(st, exact)
         if not exact:
             assert st.tail_dropped == sum(ref["tail_drops"]), f"seed {seed}"
         paired += st.paired_merges

@@ -21,10 +21,12 @@ def eng():
 
 
 def _train_native(eng, data: bytes, target: int, exact=False, word_starts=None, batch=128, next_id=256,
-                  vocab_size=None, table_log2=0, max_steps=None, sparse=None):
+                  vocab_size=None, table_log2=0, max_steps=None, sparse=None, step_log=None):
     """Drive the stepwise C-ABI directly; returns merges, final stream, live pair counts, stats.
     sparse: None = the library's policy, "dense" = dense loop only, "early" = sector-sparse
-    loop from the first step boundary where its zone fits."""
+    loop from the first step boundary where its zone fits.
+    step_log: a list that gets one (merges returned, pair_candidates, pair_rejected,
+    paired_merges) tuple per gbpe_trainer_step call, the stats read right after the call."""
     from gpubpe import _lib
     lib = _lib.load()
     ctx = eng.device
@@ -47,6 +49,10 @@ def _train_native(eng, data: bytes, target: int, exact=False, word_starts=None, 
             _lib.check(lib.gbpe_trainer_step(tr, batch, out, C.byref(nd), C.byref(es)), ctx, "step")
             merges += [list(out[4 * i:4 * i + 4]) for i in range(nd.value)]
             steps += 1
+            if step_log is not None:
+                sst = _lib.TrainerStats()
+                lib.gbpe_trainer_stats_get(tr, C.byref(sst))
+                step_log.append((nd.value, sst.pair_candidates, sst.pair_rejected, sst.paired_merges))
             if nd.value == 0 or es.value or (max_steps and steps >= max_steps):
                 break
         n = C.c_uint64()
