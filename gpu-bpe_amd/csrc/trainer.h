@@ -1006,22 +1006,29 @@ int lx_expand(gbpe_trainer* t, S* dst, uint64_t dst_cap, uint64_t* tot, const ui
     return GBPE_OK;
 }
 
-// diagnostic (GBPE_DEBUG lex_check=1): the lexicon right after a build expands back to the body
+// check (GBPE_DEBUG lex_check=1): the lexicon right after a build expands back to the
+// body, symbol for symbol, and its multiplicities are 0 exactly at the separators;
+// anything else fails the build (GBPE_E_INTERNAL)
 template <typename S>
 int lx_check(gbpe_trainer* t, const S* cur, uint32_t Zs, const LxPlan& lp) {
     hipStream_t s = t->ctx->stream;
-    int rc = GBPE_OK;
     S* chk = nullptr;
-    TR_HIP(t, pool_malloc(t->ctx, &chk, ((uint64_t)Zs + 64) * sizeof(S)));
+    auto chk_free = gbpe_scope_exit([&] { pool_free(t->ctx, chk); });   // every return path, TR_HIP's included
+    if (pool_malloc(t->ctx, &chk, ((uint64_t)Zs + 64) * sizeof(S)) != hipSuccess) {
+        chk = nullptr;
+        return gbpe_set_error(t->ctx, GBPE_E_OOM, "lex_check: hipMalloc(%u symbols) failed", Zs);
+    }
     uint64_t tot = 0;
-    rc = lx_expand<S>(t, chk, (uint64_t)Zs + 64, &tot);
-    std::vector<S> a(Zs), b(Zs);
+    const int rc = lx_expand<S>(t, chk, (uint64_t)Zs + 64, &tot);
     TR_HIP(t, hipStreamSynchronize(s));
-    TR_HIP(t, hipMemcpy(a.data(), chk, (uint64_t)Zs * sizeof(S), hipMemcpyDeviceToHost));
+    if (rc != GBPE_OK) return rc;   // nothing was written to chk
+    std::vector<S> a(Zs), b(Zs);
+    // (the expansion may be shorter than the body: compare what it wrote, report the rest through `expanded`)
+    const uint64_t ncmp = std::min<uint64_t>(tot, Zs);
+    TR_HIP(t, hipMemcpy(a.data(), chk, ncmp * sizeof(S), hipMemcpyDeviceToHost));
     TR_HIP(t, hipMemcpy(b.data(), cur, (uint64_t)Zs * sizeof(S), hipMemcpyDeviceToHost));
-    pool_free(t->ctx, chk);
-    uint64_t bad = Zs;
-    for (uint64_t i = 0; i < Zs; ++i)
+    uint64_t bad = ncmp < Zs ? ncmp : Zs;
+    for (uint64_t i = 0; i < ncmp; ++i)
         if (a[i] != b[i]) {
             bad = i;
             break;
@@ -1040,7 +1047,11 @@ int lx_check(gbpe_trainer* t, const S* cur, uint32_t Zs, const LxPlan& lp) {
             "mult_sum=%llu nonzero_body=%llu sep_mismatch=%llu\n", Zs, lp.nw,
             lp.nshort, lp.nlong, lp.T, (unsigned long long)tot, (unsigned long long)bad,
             (unsigned long long)wsum, (unsigned long long)nz, (unsigned long long)badm);
-    return rc;
+    if (bad != Zs || tot != Zs || badm)
+        return gbpe_set_error(t->ctx, GBPE_E_INTERNAL, "lex_check: the word lexicon does not expand to the body "
+                              "(first_diff=%llu expanded=%llu of %u, sep_mismatch=%llu)", (unsigned long long)bad,
+                              (unsigned long long)tot, Zs, (unsigned long long)badm);
+    return GBPE_OK;
 }
 
 // ── sector-sparse layout: allocations shared by sp_enter and the lexicon
