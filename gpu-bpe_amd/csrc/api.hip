@@ -33,6 +33,12 @@ static const char* const kKernelNames[] = {
     "k_pretok",          // PreTokenizer GPT-4 word starts (pre_tokenizer.mjs:226-292): k_pt_scan1/2 + k_pt_mark
     "k_me_walk",         // TokenizerManager.encode (tokenizer-manager.js:13-61): per-segment rank-order BPE
     "k_me_compact",      // its token compaction
+    // batched documents (gbpe_encode_batch; no reference counterpart: the reference encodes one buffer at a time)
+    "k_doc_table",            // per-document chunk counts and scratch slots + their scans: k_doc_table / k_doc_scan2 / k_doc_base
+    "k_chunk_desc",           // per-chunk descriptors {byte start, length, scratch start}
+    "k_trie_walk_batch",      // the walk from descriptors: k_trie_walk_v5_batch (packed double array) / k_trie_walk_batch
+    "k_chunk_compact_batch",  // k_chunk_compact4_batch
+    "k_doc_tok_off",          // per-document token offsets
 };
 
 // ── context memory pool (common.h GbpePool) ───────────────────────────────
@@ -132,7 +138,7 @@ hipError_t gbpe_dev_malloc(gbpe_ctx* ctx, void** p, uint64_t bytes) {
 
 extern "C" {
 
-const char* gbpe_version(void) { return "gpubpe 0.6 (gfx950, abi 6)"; }
+const char* gbpe_version(void) { return "gpubpe 0.7 (gfx950, abi 7)"; }
 
 int gbpe_abi_version(void) { return GBPE_ABI_VERSION; }
 
@@ -167,7 +173,7 @@ int gbpe_ctx_create(int device_ordinal, gbpe_ctx** out) {
         ctx->num_cu = prop.multiProcessorCount;
     }
     for (auto& ev : ctx->ev) hipEventCreate(&ev);
-    if (hipHostMalloc((void**)&ctx->enc_host_total, 16, hipHostMallocDefault) != hipSuccess) {
+    if (hipHostMalloc((void**)&ctx->enc_host_total, 64, hipHostMallocDefault) != hipSuccess) {
         hipStreamDestroy(ctx->stream);
         delete ctx;
         return GBPE_E_OOM;
@@ -184,6 +190,7 @@ void gbpe_ctx_destroy(gbpe_ctx* ctx) {
     hipFree(ctx->enc_counts);
     hipFree(ctx->enc_in);
     hipFree(ctx->enc_out);
+    hipFree(ctx->enc_docs);
     hipFree(ctx->pt_agg);
     if (ctx->enc_host_total) hipHostFree(ctx->enc_host_total);
     gbpe_pool_trim(ctx);   // (blocks still busy belong to trainers the caller did not destroy)

@@ -43,7 +43,8 @@ struct gbpe_ctx {
     void* enc_counts = nullptr;   uint64_t enc_counts_bytes = 0;
     void* enc_in = nullptr;       uint64_t enc_in_bytes = 0;
     void* enc_out = nullptr;      uint64_t enc_out_bytes = 0;
-    uint32_t* enc_host_total = nullptr;   // pinned
+    void* enc_docs = nullptr;     uint64_t enc_docs_bytes = 0;   // gbpe_encode_batch: per-document table
+    uint32_t* enc_host_total = nullptr;   // pinned, 64 bytes
     void* pt_agg = nullptr;       uint64_t pt_agg_bytes = 0;   // pre-tokenizer block aggregates
     hipEvent_t ev[8] = {};
     double enc_ms[3] = {0, 0, 0};

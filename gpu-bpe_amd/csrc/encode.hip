@@ -390,6 +390,407 @@ __global__ __launch_bounds__(256) void k_chunk_compact4(const T* __restrict__ sc
     }
 }
 
+// ── batched documents (gbpe_encode_batch): many documents laid end to end, each
+// chunked from its own first byte ("Batched documents") ──────────
+//
+// Per-document table: document d has nch[d] = ceil(len / cs) chunks and a
+// scratch slot of round_up(len, 8) token elements (a chunk's last partial
+// 16-byte token vector stays inside its document's slot, and slot starts keep
+// the vector stores aligned); the exclusive scans of both give chunk_base /
+// scr_base.  The scratch is then O(n + n_docs) elements, not nchunks * cs.
+constexpr int DOC_TPB = 1024;   // documents per table block (one lane each)
+constexpr uint32_t DOC_BAD_ORDER = 1u, DOC_BAD_FIRST = 2u, DOC_BAD_LAST = 4u;
+
+struct DocTotals {   // read back once per call (the grid and the scratch are sized from it)
+    uint64_t nchunks, scr_elems, invalid;
+};
+
+// wave-then-block exclusive scan of one u64 per thread (DOC_TPB threads); returns
+// the thread's exclusive prefix, *total = the block's sum
+__device__ __forceinline__ uint64_t doc_block_scan(uint64_t v, uint64_t* wsum, uint64_t* total) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    uint64_t incl = v;
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint64_t o = __shfl_up(incl, off);
+        if (lane >= off) incl += o;
+    }
+    if (lane == 63) wsum[wid] = incl;
+    __syncthreads();
+    uint64_t run = incl - v, all = 0;
+    for (int w = 0; w < DOC_TPB / 64; ++w) {
+        if (w < wid) run += wsum[w];
+        all += wsum[w];
+    }
+    __syncthreads();   // wsum is reused by the next scan
+    *total = all;
+    return run;
+}
+
+// one lane per document: validate its offsets, its chunk count and slot size,
+// block-local exclusive prefixes of both + the block totals
+__global__ __launch_bounds__(DOC_TPB) void k_doc_table(const uint64_t* __restrict__ doc_off, uint64_t n_docs, uint64_t n,
+                                                       uint32_t cs, uint64_t* __restrict__ chunk_base,
+                                                       uint64_t* __restrict__ scr_base, uint64_t* __restrict__ blk_ch,
+                                                       uint64_t* __restrict__ blk_scr, uint32_t* __restrict__ invalid) {
+    __shared__ uint64_t wsum[DOC_TPB / 64];
+    const uint64_t d = (uint64_t)blockIdx.x * DOC_TPB + threadIdx.x;
+    uint64_t nch = 0, slot = 0;
+    if (d < n_docs) {
+        const uint64_t a = doc_off[d], b = doc_off[d + 1];
+        uint32_t bad = 0;
+        if (b < a || b > n) bad |= DOC_BAD_ORDER;   // (b > n: a later entry decreases or the last is not n)
+        if (d == 0 && a != 0) bad |= DOC_BAD_FIRST;
+        if (d == n_docs - 1 && b != n) bad |= DOC_BAD_LAST;
+        if (bad) {
+            atomicOr(invalid, bad);
+        } else {
+            const uint64_t len = b - a;
+            nch = (len + cs - 1) / cs;
+            slot = (len + 7) & ~7ull;
+        }
+    }
+    uint64_t tot_ch, tot_scr;
+    const uint64_t pc = doc_block_scan(nch, wsum, &tot_ch);
+    const uint64_t ps = doc_block_scan(slot, wsum, &tot_scr);
+    if (d < n_docs) {
+        chunk_base[d] = pc;
+        scr_base[d] = ps;
+    }
+    if (threadIdx.x == 0) {
+        blk_ch[blockIdx.x] = tot_ch;
+        blk_scr[blockIdx.x] = tot_scr;
+    }
+}
+
+// exclusive scan of the table blocks' totals (one workgroup); writes the grand totals
+__global__ __launch_bounds__(DOC_TPB) void k_doc_scan2(uint64_t* __restrict__ blk_ch, uint64_t* __restrict__ blk_scr,
+                                                       uint64_t nblk, const uint32_t* __restrict__ invalid,
+                                                       DocTotals* __restrict__ totals) {
+    __shared__ uint64_t wsum[DOC_TPB / 64];
+    const uint64_t per = (nblk + DOC_TPB - 1) / DOC_TPB;
+    const uint64_t lo = min((uint64_t)threadIdx.x * per, nblk), hi = min(lo + per, nblk);
+    uint64_t sc = 0, ss = 0;
+    for (uint64_t i = lo; i < hi; ++i) {
+        sc += blk_ch[i];
+        ss += blk_scr[i];
+    }
+    uint64_t tot_ch, tot_scr;
+    uint64_t rc = doc_block_scan(sc, wsum, &tot_ch);
+    uint64_t rs = doc_block_scan(ss, wsum, &tot_scr);
+    for (uint64_t i = lo; i < hi; ++i) {
+        const uint64_t vc = blk_ch[i], vs = blk_scr[i];
+        blk_ch[i] = rc;
+        blk_scr[i] = rs;
+        rc += vc;
+        rs += vs;
+    }
+    if (threadIdx.x == 0) {
+        totals->nchunks = tot_ch;
+        totals->scr_elems = tot_scr;
+        totals->invalid = *invalid;
+    }
+}
+
+// block-local prefixes → global chunk_base / scr_base (entry n_docs = the totals)
+__global__ __launch_bounds__(DOC_TPB) void k_doc_base(uint64_t* __restrict__ chunk_base, uint64_t* __restrict__ scr_base,
+                                                      const uint64_t* __restrict__ blk_ch,
+                                                      const uint64_t* __restrict__ blk_scr, uint64_t n_docs,
+                                                      const DocTotals* __restrict__ totals) {
+    const uint64_t d = (uint64_t)blockIdx.x * DOC_TPB + threadIdx.x;
+    if (d < n_docs) {
+        chunk_base[d] += blk_ch[blockIdx.x];
+        scr_base[d] += blk_scr[blockIdx.x];
+    } else if (d == n_docs) {
+        chunk_base[d] = totals->nchunks;
+        scr_base[d] = totals->scr_elems;
+    }
+}
+
+// Per-chunk descriptor: where the chunk's bytes start, how many there are, and
+// where its tokens go in the scratch.
+struct __attribute__((aligned(16))) ChunkDesc {
+    uint64_t c0;    // first byte (absolute in the batch buffer)
+    uint64_t scr;   // first scratch element
+    uint32_t len;   // min(cs, document end - c0)
+    uint32_t pad[3];
+};
+static_assert(sizeof(ChunkDesc) == 32, "two 16-byte loads per descriptor");
+
+// one lane per chunk: its document is the last d with chunk_base[d] <= chunk (an
+// empty document repeats its successor's chunk_base and is stepped over)
+__global__ __launch_bounds__(256) void k_chunk_desc(const uint64_t* __restrict__ doc_off,
+                                                    const uint64_t* __restrict__ chunk_base,
+                                                    const uint64_t* __restrict__ scr_base, uint64_t n_docs, uint32_t cs,
+                                                    uint64_t nchunks, ChunkDesc* __restrict__ desc) {
+    const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= nchunks) return;
+    uint64_t lo = 0, hi = n_docs;   // chunk_base[lo] <= c < chunk_base[hi] (chunk_base[n_docs] = nchunks)
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (chunk_base[mid] <= c) lo = mid;
+        else hi = mid;
+    }
+    const uint64_t k = c - chunk_base[lo];
+    const uint64_t start = doc_off[lo] + k * cs;
+    ChunkDesc e;
+    e.c0 = start;
+    e.scr = scr_base[lo] + k * cs;
+    e.len = (uint32_t)min((uint64_t)cs, doc_off[lo + 1] - start);
+    e.pad[0] = e.pad[1] = e.pad[2] = 0;
+    desc[c] = e;
+}
+
+// k_trie_walk with the chunk taken from its descriptor; input words are read
+// aligned to the buffer and the last partial word byte by byte (inside [0, n))
+template <typename T>
+__global__ __launch_bounds__(WALK_TPB) void k_trie_walk_batch(const uint8_t* __restrict__ in, uint64_t n,
+                                                              const ChunkDesc* __restrict__ desc,
+                                                              const uint4* __restrict__ rec, uint32_t nrec,
+                                                              const uint4* __restrict__ root, T* __restrict__ scratch,
+                                                              uint32_t* __restrict__ counts, uint64_t nchunks) {
+    __shared__ uint4 lut[256];   // byte -> {state, base, tokenId, present}
+    lut[threadIdx.x] = root[threadIdx.x];
+    __syncthreads();
+    const uint64_t chunk = (uint64_t)blockIdx.x * WALK_TPB + threadIdx.x;
+    if (chunk >= nchunks) return;
+    const ChunkDesc dsc = desc[chunk];
+    const uint64_t c0 = dsc.c0;
+    const uint64_t ce = c0 + dsc.len;
+    T* out = scratch + dsc.scr;
+    const uint32_t* in32 = reinterpret_cast<const uint32_t*>(in);
+    uint64_t widx = ~0ull;
+    uint32_t word = 0;
+    auto byte_at = [&](uint64_t p) -> uint32_t {
+        const uint64_t wi = p >> 2;
+        if (wi != widx) {
+            if (wi * 4 + 4 <= n) {
+                word = in32[wi];
+            } else {
+                word = 0;
+                for (uint64_t j = wi * 4; j < n; ++j) word |= (uint32_t)in[j] << ((j & 3u) * 8u);
+            }
+            widx = wi;
+        }
+        return (word >> ((p & 3u) * 8u)) & 0xFFu;
+    };
+    uint32_t cnt = 0;
+    uint64_t pos = c0;
+    while (pos < ce) {
+        const uint32_t c = byte_at(pos);
+        const uint4 e = lut[c];
+        uint32_t lmt = INV;
+        uint64_t lmp = pos;
+        if (e.w) {
+            uint32_t s = e.x, base = e.y;
+            if (e.z != INV) {
+                lmt = e.z;
+                lmp = pos + 1;
+            }
+            uint64_t wp = pos + 1;
+            while (wp < ce) {
+                const uint32_t t = base + byte_at(wp);
+                if (t >= nrec) break;
+                const uint4 r = rec[t];
+                if (r.x != s) break;
+                s = t;
+                base = r.y;
+                ++wp;
+                if (r.z != INV) {
+                    lmt = r.z;
+                    lmp = wp;
+                }
+            }
+        }
+        if (lmt != INV) {
+            out[cnt++] = (T)lmt;
+            pos = lmp;
+        } else {   // no token starts here: emit the raw byte value (tokenize.wgsl:169-171)
+            out[cnt++] = (T)c;
+            ++pos;
+        }
+    }
+    counts[chunk] = cnt;
+}
+
+// k_trie_walk_v5 with the chunk taken from its descriptor.  A chunk starts on any
+// byte, so the 64-byte windows are aligned to the BUFFER (the window base is the
+// chunk start rounded down to 64; the chunk's first byte sits at offset c0 & 63 of
+// its first window): every refill is still one whole cache line and one aligned
+// 4 x 16-byte load.  A window may hold bytes of the neighbouring documents; the
+// walk only ever asks for bytes below its own `ce`.  Token vectors go to the
+// document's slot (scr_base and cs are multiples of 8: 16-byte aligned stores).
+template <typename T>
+__global__ __launch_bounds__(WALK_TPB) void k_trie_walk_v5_batch(const uint8_t* __restrict__ in, uint64_t n,
+                                                                 const ChunkDesc* __restrict__ desc,
+                                                                 const uint2* __restrict__ rec, uint32_t nrec,
+                                                                 uint32_t root_base, T* __restrict__ scratch,
+                                                                 uint32_t* __restrict__ counts, uint64_t nchunks) {
+    constexpr uint32_t PER = 16 / sizeof(T);
+    __shared__ uint2 lut[256];
+    {
+        const uint32_t t = root_base + threadIdx.x;
+        lut[threadIdx.x] = t < nrec ? rec[t] : make_uint2(0x3FFFFFu, 0u);
+    }
+    __syncthreads();
+    const uint64_t chunk = (uint64_t)blockIdx.x * WALK_TPB + threadIdx.x;
+    if (chunk >= nchunks) return;
+    const ChunkDesc dsc = desc[chunk];
+    const uint64_t a0 = dsc.c0 & ~63ull;            // the first window's base, aligned to the buffer
+    const uint32_t sh = (uint32_t)(dsc.c0 & 63u);   // the chunk's first byte inside it
+    const uint32_t ce = dsc.len;
+    T* out = scratch + dsc.scr;
+    uint32_t cb = ~0u;
+    Win64 w64{};
+    uint4 acc = make_uint4(0, 0, 0, 0);
+    auto byte_at = [&](uint32_t p) -> uint32_t {
+        const uint32_t q = p + sh;   // (cs <= 2^31: no wrap)
+        const uint32_t b = q & ~63u;
+        if (b != cb) {
+            cb = b;
+            w64 = load_win64(in, n, a0 + b);
+        }
+        return win64_byte(w64, q & 63u);
+    };
+    uint32_t cnt = 0, nq = 0;
+    uint4 q[WALK_QV > 1 ? WALK_QV - 1 : 1];   // q[WALK_QV-1-nq ..]: the nq waiting vectors, oldest first
+    auto emit = [&](uint32_t tok) {
+        vec_put<T>(acc, cnt % PER, tok);
+        if (++cnt % PER == 0) {
+            if (nq == WALK_QV - 1) {
+                uint4* o = reinterpret_cast<uint4*>(out + cnt) - WALK_QV;
+#pragma unroll
+                for (uint32_t i = 0; i + 1 < WALK_QV; ++i) o[i] = q[i];
+                o[WALK_QV - 1] = acc;
+                nq = 0;
+            } else {
+                if constexpr (WALK_QV > 1) {
+#pragma unroll
+                    for (uint32_t i = 0; i + 2 < WALK_QV; ++i) q[i] = q[i + 1];
+                    q[WALK_QV - 2] = acc;
+                }
+                ++nq;
+            }
+            acc = make_uint4(0, 0, 0, 0);
+        }
+    };
+    auto flush = [&]() {   // the waiting vectors end where the partial vector starts
+        if constexpr (WALK_QV > 1) {
+            uint4* o = reinterpret_cast<uint4*>(out + (cnt / PER) * PER);
+#pragma unroll
+            for (uint32_t i = 0; i + 1 < WALK_QV; ++i)
+                if (i + nq >= WALK_QV - 1) o[(int)i - (int)WALK_QV + 1] = q[i];
+            nq = 0;
+        }
+    };
+    uint32_t pos = 0, wp = 0, lmp = 0, st = 0, base = 0, lmt = TID_NONE, first = 0;
+    bool walking = false;
+    while (pos < ce) {
+        if (!walking) {   // a token start: LDS only
+            first = byte_at(pos);
+            const uint2 e = lut[first];
+            const uint32_t tid = rec_tid(e);
+            if (rec_check(e) != 0u || rec_base(e) == 0u || pos + 1 >= ce) {
+                emit(rec_check(e) == 0u && tid != TID_NONE ? tid : first);
+                ++pos;
+                continue;
+            }
+            st = root_base + first;
+            base = rec_base(e);
+            lmt = tid;
+            lmp = pos + 1;
+            wp = pos + 1;
+            walking = true;
+        }
+        // one trie transition: the trip's L2 load
+        const uint32_t t = base + byte_at(wp);
+        const uint2 r = t < nrec ? rec[t] : make_uint2(0x3FFFFFu, 0u);
+        bool end = true;
+        if (rec_check(r) == st) {
+            st = t;
+            base = rec_base(r);
+            ++wp;
+            const uint32_t tid = rec_tid(r);
+            if (tid != TID_NONE) {
+                lmt = tid;
+                lmp = wp;
+            }
+            end = base == 0u || wp >= ce;
+        }
+        if (end) {   // the longest match ends: emit it (or the raw first byte), restart after it
+            const bool hit = lmt != TID_NONE;
+            emit(hit ? lmt : first);
+            pos = hit ? lmp : pos + 1;
+            walking = false;
+        }
+    }
+    flush();
+    // (at most PER - 1 elements past the count: inside the document's rounded slot)
+    if (cnt % PER) *reinterpret_cast<uint4*>(out + (cnt / PER) * PER) = acc;
+    counts[chunk] = cnt;
+}
+
+// k_chunk_compact4 with each chunk's source taken from its descriptor
+template <typename T>
+__global__ __launch_bounds__(256) void k_chunk_compact4_batch(const T* __restrict__ scratch,
+                                                              const ChunkDesc* __restrict__ desc,
+                                                              const uint32_t* __restrict__ counts,
+                                                              const uint32_t* __restrict__ local,
+                                                              const uint64_t* __restrict__ blocksum, uint64_t nchunks,
+                                                              uint32_t* __restrict__ out, uint64_t out_cap) {
+    __shared__ uint64_t s_off[4 * CPW];
+    __shared__ uint64_t s_src[4 * CPW];
+    __shared__ uint32_t s_cnt[4 * CPW];
+    const uint64_t c0 = (uint64_t)blockIdx.x * (4 * CPW);
+    if (threadIdx.x < 4 * CPW) {
+        const uint64_t c = c0 + threadIdx.x;
+        s_cnt[threadIdx.x] = c < nchunks ? counts[c] : 0u;
+        s_off[threadIdx.x] = c < nchunks ? blocksum[c / SCAN_BLK] + local[c] : 0ull;
+        s_src[threadIdx.x] = c < nchunks ? desc[c].scr : 0ull;
+    }
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    uint32_t most = 0;
+#pragma unroll
+    for (int q = 0; q < CPW; ++q) most = max(most, s_cnt[wid * CPW + q]);
+    for (uint32_t b0 = 0; b0 < most; b0 += 256) {
+        uint32_t v[CPW][4];
+#pragma unroll
+        for (int q = 0; q < CPW; ++q) {
+            const uint32_t cnt = s_cnt[wid * CPW + q];
+            const T* src = scratch + s_src[wid * CPW + q];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t j = b0 + lane + 64u * k;
+                v[q][k] = j < cnt ? (uint32_t)src[j] : 0u;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < CPW; ++q) {
+            const uint32_t cnt = s_cnt[wid * CPW + q];
+            const uint64_t off = s_off[wid * CPW + q];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t j = b0 + lane + 64u * k;
+                if (j < cnt && off + j < out_cap) out[off + j] = v[q][k];
+            }
+        }
+    }
+}
+
+// one lane per document (+ the closing entry): its first token's position — the
+// scanned offset of its first chunk; a document without chunks starts where the
+// next one with chunks does, or at the total
+__global__ __launch_bounds__(256) void k_doc_tok_off(const uint64_t* __restrict__ chunk_base,
+                                                     const uint32_t* __restrict__ local,
+                                                     const uint64_t* __restrict__ blocksum,
+                                                     const uint64_t* __restrict__ total, uint64_t n_docs,
+                                                     uint64_t nchunks, uint64_t* __restrict__ tok_off) {
+    const uint64_t d = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (d > n_docs) return;
+    const uint64_t c = d < n_docs ? chunk_base[d] : nchunks;
+    tok_off[d] = c < nchunks ? blocksum[c / SCAN_BLK] + local[c] : *total;
+}
+
 }  // namespace
 
 struct gbpe_trie {
@@ -632,7 +1033,233 @@ int encode_device_impl(gbpe_ctx* ctx, gbpe_trie* tr, const uint8_t* d_in, uint64
     return GBPE_OK;
 }
 
+// bytes of ctx->enc_docs the batch encode's per-document table takes for n_docs
+// documents: chunk_base + scr_base (n_docs + 1 each), the table blocks' totals
+// (two arrays), the grand totals and the invalid flag
+uint64_t doc_table_bytes(uint64_t n_docs) {
+    const uint64_t ndblk = gbpe_div_up(n_docs, DOC_TPB);
+    return 2 * (n_docs + 1) * 8 + 2 * (ndblk + 1) * 8 + sizeof(DocTotals) + 8 + 64;
+}
+
+int doc_offsets_error(gbpe_ctx* ctx, uint32_t bad) {
+    return gbpe_set_error(ctx, GBPE_E_INVALID, "encode batch: document offsets %s",
+                          (bad & DOC_BAD_FIRST)   ? "do not start at 0"
+                          : (bad & DOC_BAD_ORDER) ? "decrease (or pass the end of the bytes)"
+                                                  : "do not end at the byte count");
+}
+
+// The batch pipeline on device buffers (n, n_docs > 0): table + scans (one
+// readback: the chunk count sizes the grid, the slot total the scratch),
+// descriptors, walk, count scan, compact, document token offsets.
+int encode_batch_device_impl(gbpe_ctx* ctx, gbpe_trie* tr, const uint8_t* d_in, uint64_t n, const uint64_t* d_doc_off,
+                             uint64_t n_docs, uint32_t cs, uint32_t* d_out, uint64_t out_cap, uint64_t* d_tok_off,
+                             uint64_t* n_out) {
+    hipStream_t s = ctx->stream;
+    const bool narrow = tr->max_token_id < 65536u;   // raw-byte fallbacks are < 256
+    const uint64_t esz = narrow ? 2 : 4;
+    const uint64_t ndblk = gbpe_div_up(n_docs, DOC_TPB);
+    int rc = grow(ctx, &ctx->enc_docs, &ctx->enc_docs_bytes, doc_table_bytes(n_docs));
+    if (rc != GBPE_OK) return rc;
+    uint64_t* chunk_base = (uint64_t*)ctx->enc_docs;
+    uint64_t* scr_base = chunk_base + n_docs + 1;
+    uint64_t* blk_ch = scr_base + n_docs + 1;
+    uint64_t* blk_scr = blk_ch + ndblk + 1;
+    DocTotals* d_totals = (DocTotals*)(blk_scr + ndblk + 1);
+    uint32_t* d_invalid = (uint32_t*)(d_totals + 1);
+    GBPE_HIP(ctx, hipMemsetAsync(d_invalid, 0, 4, s));
+    GBPE_HIP(ctx, hipEventRecord(ctx->ev[4], s));
+    hipLaunchKernelGGL(k_doc_table, dim3((uint32_t)ndblk), dim3(DOC_TPB), 0, s, d_doc_off, n_docs, n, cs, chunk_base,
+                       scr_base, blk_ch, blk_scr, d_invalid);
+    hipLaunchKernelGGL(k_doc_scan2, dim3(1), dim3(DOC_TPB), 0, s, blk_ch, blk_scr, ndblk, (const uint32_t*)d_invalid,
+                       d_totals);
+    hipLaunchKernelGGL(k_doc_base, dim3((uint32_t)gbpe_div_up(n_docs + 1, DOC_TPB)), dim3(DOC_TPB), 0, s, chunk_base,
+                       scr_base, (const uint64_t*)blk_ch, (const uint64_t*)blk_scr, n_docs, (const DocTotals*)d_totals);
+    GBPE_LAUNCH_CHECK(ctx);
+    GBPE_HIP(ctx, hipEventRecord(ctx->ev[5], s));
+    GBPE_HIP(ctx, hipMemcpyAsync(ctx->enc_host_total, d_totals, sizeof(DocTotals), hipMemcpyDeviceToHost, s));
+    GBPE_HIP(ctx, hipStreamSynchronize(s));
+    DocTotals tot;
+    memcpy(&tot, ctx->enc_host_total, sizeof(tot));
+    if (tot.invalid) return doc_offsets_error(ctx, (uint32_t)tot.invalid);   // nothing else was launched
+    const uint64_t nchunks = tot.nchunks;
+    if (nchunks == 0) return gbpe_set_error(ctx, GBPE_E_INTERNAL, "encode batch: no chunks for %llu bytes", (unsigned long long)n);
+    const uint64_t nblk = gbpe_div_up(nchunks, SCAN_BLK);
+    // scratch: one rounded slot per document, O(n + n_docs) elements
+    rc = grow(ctx, &ctx->enc_scratch, &ctx->enc_scratch_bytes, tot.scr_elems * esz + 16);
+    if (rc == GBPE_OK)
+        rc = grow(ctx, &ctx->enc_counts, &ctx->enc_counts_bytes,
+                  nchunks * 8 + nblk * 8 + 64 + 16 + nchunks * sizeof(ChunkDesc));
+    if (rc != GBPE_OK) return rc;
+    uint32_t* counts = (uint32_t*)ctx->enc_counts;
+    uint32_t* local = counts + nchunks;
+    uint64_t* blocksum = (uint64_t*)(((uintptr_t)(local + nchunks) + 15) & ~(uintptr_t)15);
+    uint64_t* d_total = blocksum + nblk + 1;
+    ChunkDesc* desc = (ChunkDesc*)(((uintptr_t)(d_total + 1) + 15) & ~(uintptr_t)15);
+    const uint32_t gw = (uint32_t)gbpe_div_up(nchunks, WALK_TPB);
+    GBPE_HIP(ctx, hipEventRecord(ctx->ev[6], s));
+    hipLaunchKernelGGL(k_chunk_desc, dim3((uint32_t)gbpe_div_up(nchunks, 256)), dim3(256), 0, s, d_doc_off,
+                       (const uint64_t*)chunk_base, (const uint64_t*)scr_base, n_docs, cs, nchunks, desc);
+    GBPE_LAUNCH_CHECK(ctx);
+    GBPE_HIP(ctx, hipEventRecord(ctx->ev[0], s));
+    // path selection as in encode_device_impl
+    const bool packed = (cs % 8u) == 0u && tr->rec2;
+    const uint32_t nrec2 = tr->nrec + 256;
+    if (packed && narrow)
+        hipLaunchKernelGGL(k_trie_walk_v5_batch<uint16_t>, dim3(gw), dim3(WALK_TPB), 0, s, d_in, n, (const ChunkDesc*)desc,
+                           tr->rec2, nrec2, tr->root_base, (uint16_t*)ctx->enc_scratch, counts, nchunks);
+    else if (packed)
+        hipLaunchKernelGGL(k_trie_walk_v5_batch<uint32_t>, dim3(gw), dim3(WALK_TPB), 0, s, d_in, n, (const ChunkDesc*)desc,
+                           tr->rec2, nrec2, tr->root_base, (uint32_t*)ctx->enc_scratch, counts, nchunks);
+    else if (narrow)
+        hipLaunchKernelGGL(k_trie_walk_batch<uint16_t>, dim3(gw), dim3(WALK_TPB), 0, s, d_in, n, (const ChunkDesc*)desc,
+                           tr->rec, tr->nrec, tr->root, (uint16_t*)ctx->enc_scratch, counts, nchunks);
+    else
+        hipLaunchKernelGGL(k_trie_walk_batch<uint32_t>, dim3(gw), dim3(WALK_TPB), 0, s, d_in, n, (const ChunkDesc*)desc,
+                           tr->rec, tr->nrec, tr->root, (uint32_t*)ctx->enc_scratch, counts, nchunks);
+    GBPE_LAUNCH_CHECK(ctx);
+    GBPE_HIP(ctx, hipEventRecord(ctx->ev[1], s));
+    hipLaunchKernelGGL(k_chunk_scan1, dim3((uint32_t)nblk), dim3(SCAN_TPB), 0, s, (const uint32_t*)counts, nchunks, local,
+                       blocksum);
+    hipLaunchKernelGGL(k_chunk_scan2, dim3(1), dim3(SCAN_TPB), 0, s, blocksum, nblk, d_total);
+    GBPE_LAUNCH_CHECK(ctx);
+    GBPE_HIP(ctx, hipEventRecord(ctx->ev[2], s));
+    const uint32_t gc4 = (uint32_t)gbpe_div_up(nchunks, 4 * CPW);
+    if (narrow)
+        hipLaunchKernelGGL(k_chunk_compact4_batch<uint16_t>, dim3(gc4), dim3(256), 0, s,
+                           (const uint16_t*)ctx->enc_scratch, (const ChunkDesc*)desc, (const uint32_t*)counts,
+                           (const uint32_t*)local, (const uint64_t*)blocksum, nchunks, d_out, out_cap);
+    else
+        hipLaunchKernelGGL(k_chunk_compact4_batch<uint32_t>, dim3(gc4), dim3(256), 0, s,
+                           (const uint32_t*)ctx->enc_scratch, (const ChunkDesc*)desc, (const uint32_t*)counts,
+                           (const uint32_t*)local, (const uint64_t*)blocksum, nchunks, d_out, out_cap);
+    // (runs whether or not the tokens fit: tok_off is complete on GBPE_E_CAPACITY)
+    hipLaunchKernelGGL(k_doc_tok_off, dim3((uint32_t)gbpe_div_up(n_docs + 1, 256)), dim3(256), 0, s,
+                       (const uint64_t*)chunk_base, (const uint32_t*)local, (const uint64_t*)blocksum,
+                       (const uint64_t*)d_total, n_docs, nchunks, d_tok_off);
+    GBPE_LAUNCH_CHECK(ctx);
+    GBPE_HIP(ctx, hipEventRecord(ctx->ev[3], s));
+    GBPE_HIP(ctx, hipMemcpyAsync(ctx->enc_host_total, d_total, 8, hipMemcpyDeviceToHost, s));
+    GBPE_HIP(ctx, hipStreamSynchronize(s));
+    float a = 0, b = 0, c = 0, t0 = 0, t1 = 0;
+    hipEventElapsedTime(&t0, ctx->ev[4], ctx->ev[5]);
+    hipEventElapsedTime(&t1, ctx->ev[6], ctx->ev[0]);
+    hipEventElapsedTime(&a, ctx->ev[0], ctx->ev[1]);
+    hipEventElapsedTime(&b, ctx->ev[1], ctx->ev[2]);
+    hipEventElapsedTime(&c, ctx->ev[2], ctx->ev[3]);
+    ctx->enc_ms[0] = a;
+    ctx->enc_ms[1] = (double)t0 + t1 + b;   // every scan and table kernel
+    ctx->enc_ms[2] = c;
+    uint64_t total;
+    memcpy(&total, ctx->enc_host_total, 8);
+    *n_out = total;
+    if (total > out_cap)
+        return gbpe_set_error(ctx, GBPE_E_CAPACITY, "encode batch: output needs %llu tokens", (unsigned long long)total);
+    return GBPE_OK;
+}
+
+constexpr uint32_t kBatchMaxChunk = 1u << 31;   // the batch walk's in-chunk positions are 32-bit
+
 }  // namespace
+
+extern "C" int gbpe_encode_batch_device(gbpe_ctx* ctx, gbpe_trie* tr, const void* d_bytes, uint64_t n,
+                                        const void* d_doc_off, uint64_t n_docs, uint32_t chunk_size, void* d_out,
+                                        uint64_t out_cap, void* d_tok_off, uint64_t* n_out) {
+    if (!ctx || !tr || !n_out || !d_tok_off || (n_docs && !d_doc_off) || (n && n_docs && (!d_bytes || (!d_out && out_cap))))
+        return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
+    if ((uintptr_t)d_bytes & 15u) return gbpe_set_error(ctx, GBPE_E_INVALID, "d_bytes must be 16-byte aligned");
+    if (((uintptr_t)d_doc_off | (uintptr_t)d_tok_off) & 7u)
+        return gbpe_set_error(ctx, GBPE_E_INVALID, "d_doc_off and d_tok_off must be 8-byte aligned");
+    const uint32_t cs = effective_cs(tr, chunk_size);
+    if (cs > kBatchMaxChunk) return gbpe_set_error(ctx, GBPE_E_INVALID, "encode batch: chunk size above 2^31");
+    *n_out = 0;
+    if (n_docs == 0 || n == 0) {
+        GBPE_HIP(ctx, hipMemsetAsync(d_tok_off, 0, (n_docs + 1) * 8, ctx->stream));
+        GBPE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return GBPE_OK;
+    }
+    return encode_batch_device_impl(ctx, tr, (const uint8_t*)d_bytes, n, (const uint64_t*)d_doc_off, n_docs, cs,
+                                    (uint32_t*)d_out, out_cap, (uint64_t*)d_tok_off, n_out);
+}
+
+// Host buffers in and out.  The offsets are checked here, before anything is
+// launched.  Inputs above the encode slice run as groups of whole documents (a
+// document above the slice is its own group), one group after the other through the
+// device pipeline: a group's bytes, its offsets rebased to its first byte, and back
+// its tokens and token offsets, which the running total shifts.
+extern "C" int gbpe_encode_batch(gbpe_ctx* ctx, gbpe_trie* tr, const uint8_t* bytes, uint64_t n, const uint64_t* doc_off,
+                                 uint64_t n_docs, uint32_t chunk_size, uint32_t* out, uint64_t out_cap,
+                                 uint64_t* tok_off, uint64_t* n_out) {
+    if (!ctx || !tr || !n_out || !tok_off || (n_docs && !doc_off) || (n && !bytes) || (out_cap && !out))
+        return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
+    *n_out = 0;
+    if (n_docs == 0) {
+        tok_off[0] = 0;
+        return GBPE_OK;
+    }
+    if (doc_off[0] != 0) return doc_offsets_error(ctx, DOC_BAD_FIRST);
+    for (uint64_t d = 0; d < n_docs; ++d)
+        if (doc_off[d + 1] < doc_off[d]) return doc_offsets_error(ctx, DOC_BAD_ORDER);
+    if (doc_off[n_docs] != n) return doc_offsets_error(ctx, DOC_BAD_LAST);
+    const uint32_t cs = effective_cs(tr, chunk_size);
+    if (cs > kBatchMaxChunk) return gbpe_set_error(ctx, GBPE_E_INVALID, "encode batch: chunk size above 2^31");
+    if (n == 0) {
+        for (uint64_t d = 0; d <= n_docs; ++d) tok_off[d] = 0;
+        return GBPE_OK;
+    }
+    const uint64_t slice = (uint64_t)std::max<long>(1, gbpe_debug_knob("encode_slice", (long)kEncSlice));
+    // the groups: [g0, g1) with at most `slice` bytes, or one document
+    auto group_end = [&](uint64_t g0) {
+        uint64_t g1 = g0 + 1;
+        while (g1 < n_docs && doc_off[g1 + 1] - doc_off[g0] <= slice) ++g1;
+        return g1;
+    };
+    uint64_t max_bytes = 0, max_docs = 0;
+    for (uint64_t g0 = 0; g0 < n_docs;) {
+        const uint64_t g1 = group_end(g0);
+        max_bytes = std::max(max_bytes, doc_off[g1] - doc_off[g0]);
+        max_docs = std::max(max_docs, g1 - g0);
+        g0 = g1;
+    }
+    const uint64_t table = (doc_table_bytes(max_docs) + 15) & ~15ull;
+    int rc = grow(ctx, &ctx->enc_in, &ctx->enc_in_bytes, max_bytes + 64);
+    if (rc == GBPE_OK) rc = grow(ctx, &ctx->enc_out, &ctx->enc_out_bytes, max_bytes * 4 + 16);   // <= 1 token per byte
+    if (rc == GBPE_OK) rc = grow(ctx, &ctx->enc_docs, &ctx->enc_docs_bytes, table + 2 * (max_docs + 1) * 8);
+    if (rc != GBPE_OK) return rc;
+    uint8_t* d_in = (uint8_t*)ctx->enc_in;
+    uint32_t* d_out = (uint32_t*)ctx->enc_out;
+    uint64_t* d_doc_off = (uint64_t*)((uint8_t*)ctx->enc_docs + table);   // (behind the impl's table)
+    uint64_t* d_tok_off = d_doc_off + max_docs + 1;
+    std::vector<uint64_t> rel;
+    uint64_t total = 0;
+    for (uint64_t g0 = 0; g0 < n_docs;) {
+        const uint64_t g1 = group_end(g0), nd = g1 - g0;
+        const uint64_t b0 = doc_off[g0], len = doc_off[g1] - b0;
+        if (len == 0) {   // empty documents only
+            for (uint64_t d = g0; d <= g1; ++d) tok_off[d] = total;
+            g0 = g1;
+            continue;
+        }
+        rel.resize(nd + 1);
+        for (uint64_t d = 0; d <= nd; ++d) rel[d] = doc_off[g0 + d] - b0;
+        GBPE_HIP(ctx, hipMemcpyAsync(d_in, bytes + b0, len, hipMemcpyHostToDevice, ctx->stream));
+        GBPE_HIP(ctx, hipMemcpyAsync(d_doc_off, rel.data(), (nd + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        GBPE_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (rel is reused by the next group)
+        uint64_t t = 0;
+        rc = encode_batch_device_impl(ctx, tr, d_in, len, d_doc_off, nd, cs, d_out, len, d_tok_off, &t);
+        if (rc != GBPE_OK) return rc;
+        GBPE_HIP(ctx, hipMemcpyAsync(tok_off + g0, d_tok_off, (nd + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+        const uint64_t fit = total < out_cap ? std::min(t, out_cap - total) : 0;   // never at or beyond out[out_cap]
+        if (fit) GBPE_HIP(ctx, hipMemcpyAsync(out + total, d_out, fit * 4, hipMemcpyDeviceToHost, ctx->stream));
+        GBPE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (uint64_t d = g0; d <= g1; ++d) tok_off[d] += total;
+        total += t;
+        g0 = g1;
+    }
+    *n_out = total;
+    if (total > out_cap)
+        return gbpe_set_error(ctx, GBPE_E_CAPACITY, "encode batch: output needs %llu tokens", (unsigned long long)total);
+    return GBPE_OK;
+}
 
 extern "C" int gbpe_encode_device(gbpe_ctx* ctx, gbpe_trie* tr, const void* d_bytes, uint64_t n, uint32_t chunk_size,
                                   void* d_out, uint64_t out_cap, uint64_t* n_out) {

@@ -16,6 +16,7 @@
 //   trainerDestroy(trainer)
 //   trieUpload(ctx, nodes: Uint32Array, edges: Uint32Array) -> trie      trieFree(trie)
 //   encode(ctx, trie, bytes, chunkSize) -> Promise<Uint32Array>
+//   encodeBatch(ctx, trie, bytes, offsets: Float64Array, chunkSize) -> Promise<{tokens: Uint32Array, offsets: Float64Array}>
 //   wordBoundary(ctx, bytes) -> Uint8Array
 //
 // Concurrency and lifetimes.  Every call that touches a context's device state
@@ -628,6 +629,110 @@ napi_value Encode(napi_env env, napi_callback_info info) {
     return promise;
 }
 
+// encodeBatch: many documents in one call (gbpe_encode_batch; an addition to the
+// reference's API).  Offsets cross the boundary as Float64Array (exact below 2^53).
+struct EncodeBatchWork {
+    napi_async_work work = nullptr;
+    napi_deferred deferred = nullptr;
+    napi_ref keep_in = nullptr, keep_ctx = nullptr, keep_trie = nullptr;
+    Ctx* c = nullptr;
+    Trie* trie = nullptr;
+    const uint8_t* data = nullptr;
+    size_t len = 0;
+    uint32_t cs = 0;
+    std::vector<uint64_t> doc_off, tok_off;   // (the offsets are copied on the JS thread)
+    std::vector<uint32_t> out;
+    uint64_t n_out = 0;
+    int rc = GBPE_OK;
+    std::string err;
+};
+
+void encode_batch_execute(napi_env, void* data) {
+    auto* w = static_cast<EncodeBatchWork*>(data);
+    w->out.resize(w->len ? w->len : 1);
+    w->tok_off.assign(w->doc_off.size(), 0);
+    std::lock_guard<std::mutex> g(w->c->mu);
+    w->rc = gbpe_encode_batch(w->c->ctx, w->trie->trie, w->data, w->len, w->doc_off.data(), w->doc_off.size() - 1, w->cs,
+                              w->out.data(), w->len, w->tok_off.data(), &w->n_out);
+    if (w->rc != GBPE_OK) w->err = last_error(w->c->ctx, "encode batch", w->rc);
+}
+
+void encode_batch_complete(napi_env env, napi_status, void* data) {
+    auto* w = static_cast<EncodeBatchWork*>(data);
+    if (w->rc != GBPE_OK) {
+        napi_value msg, err;
+        napi_create_string_utf8(env, w->err.c_str(), NAPI_AUTO_LENGTH, &msg);
+        napi_create_error(env, nullptr, msg, &err);
+        napi_reject_deferred(env, w->deferred, err);
+    } else {
+        napi_value obj, ab, offs;
+        void* dst = nullptr;
+        napi_create_object(env, &obj);
+        napi_set_named_property(env, obj, "tokens", make_u32_array(env, w->out.data(), (size_t)w->n_out));
+        const size_t no = w->tok_off.size();
+        napi_create_arraybuffer(env, no * 8, &dst, &ab);
+        for (size_t i = 0; i < no; ++i) static_cast<double*>(dst)[i] = (double)w->tok_off[i];
+        napi_create_typedarray(env, napi_float64_array, no, ab, 0, &offs);
+        napi_set_named_property(env, obj, "offsets", offs);
+        napi_resolve_deferred(env, w->deferred, obj);
+    }
+    if (--w->trie->inflight == 0 && w->trie->destroy_pending) trie_free(w->trie);
+    ctx_release(w->c);
+    napi_delete_reference(env, w->keep_in);
+    napi_delete_reference(env, w->keep_ctx);
+    napi_delete_reference(env, w->keep_trie);
+    napi_delete_async_work(env, w->work);
+    delete w;
+}
+
+napi_value EncodeBatch(napi_env env, napi_callback_info info) {
+    size_t argc = 5;
+    napi_value argv[5];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Ctx* c = argc >= 1 ? unwrap_external<Ctx>(env, argv[0]) : nullptr;
+    Trie* tr = argc >= 2 ? unwrap_external<Trie>(env, argv[1]) : nullptr;
+    const uint8_t* data = nullptr;
+    size_t len = 0, noff = 0, ooff = 0;
+    bool ok = ctx_usable(c) && tr && tr->trie && !tr->destroy_pending && argc >= 5 && get_bytes(env, argv[2], &data, &len);
+    napi_typedarray_type type = napi_uint8_array;
+    void* raw = nullptr;
+    napi_value oab;
+    bool is_ta = false;
+    if (ok) napi_is_typedarray(env, argv[3], &is_ta);
+    ok = ok && is_ta && napi_get_typedarray_info(env, argv[3], &type, &noff, &raw, &oab, &ooff) == napi_ok &&
+         type == napi_float64_array && noff >= 1;
+    if (!ok) {
+        napi_throw_type_error(env, nullptr, "encodeBatch(ctx, trie, Uint8Array, offsets: Float64Array, chunkSize)");
+        return nullptr;
+    }
+    const double* offs = static_cast<const double*>(raw);
+    for (size_t i = 0; i < noff; ++i) {
+        if (!(offs[i] >= 0 && offs[i] <= 9007199254740992.0) || offs[i] != (double)(uint64_t)offs[i]) {
+            napi_throw_range_error(env, nullptr, "encodeBatch: offsets must be non-negative integers");
+            return nullptr;
+        }
+    }
+    auto* w = new EncodeBatchWork();
+    w->doc_off.resize(noff);
+    for (size_t i = 0; i < noff; ++i) w->doc_off[i] = (uint64_t)offs[i];
+    w->c = c;
+    ++c->refs;        // released by encode_batch_complete
+    w->trie = tr;
+    ++tr->inflight;
+    w->data = data;
+    w->len = len;
+    napi_get_value_uint32(env, argv[4], &w->cs);
+    napi_value promise, name;
+    NAPI_CALL(env, napi_create_promise(env, &w->deferred, &promise));
+    NAPI_CALL(env, napi_create_reference(env, argv[2], 1, &w->keep_in));
+    NAPI_CALL(env, napi_create_reference(env, argv[0], 1, &w->keep_ctx));
+    NAPI_CALL(env, napi_create_reference(env, argv[1], 1, &w->keep_trie));
+    NAPI_CALL(env, napi_create_string_utf8(env, "gpubpe.encodeBatch", NAPI_AUTO_LENGTH, &name));
+    NAPI_CALL(env, napi_create_async_work(env, nullptr, name, encode_batch_execute, encode_batch_complete, w, &w->work));
+    NAPI_CALL(env, napi_queue_async_work(env, w->work));
+    return promise;
+}
+
 napi_value Init(napi_env env, napi_value exports) {
     napi_property_descriptor props[] = {
         {"createContext", nullptr, CreateContext, nullptr, nullptr, nullptr, napi_default, nullptr},
@@ -644,6 +749,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"bpeEncode", nullptr, BpeEncode, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"trieFree", nullptr, TrieFree, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"encode", nullptr, Encode, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"encodeBatch", nullptr, EncodeBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
     };
     napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
     return exports;

@@ -40,6 +40,24 @@ export class TrieTokenizer {
         return native().encode(this._engine.device, this._trie, bytes, this._chunkSize);
     }
 
+    /**
+     * Many documents in one device call (an addition to the reference's API):
+     * one Uint32Array per document, each what encodeBytes returns for that
+     * document alone, all views into one shared buffer.
+     */
+    async encodeBatch(docs) {
+        const offsets = new Float64Array(docs.length + 1);
+        for (let d = 0; d < docs.length; d++) offsets[d + 1] = offsets[d] + docs[d].length;
+        const total = offsets[docs.length];
+        if (docs.length === 0 || total === 0) return docs.map(function () { return new Uint32Array(0); });
+        const bytes = new Uint8Array(total);
+        for (let d = 0; d < docs.length; d++) bytes.set(docs[d], offsets[d]);
+        const r = await native().encodeBatch(this._engine.device, this._trie, bytes, offsets, this._chunkSize);
+        const views = [];
+        for (let d = 0; d < docs.length; d++) views.push(r.tokens.subarray(r.offsets[d], r.offsets[d + 1]));
+        return views;
+    }
+
     decode(tokens) {
         let total = 0;
         const parts = [];

@@ -28,7 +28,8 @@
 extern "C" {
 #endif
 
-#define GBPE_ABI_VERSION 6   /* 6: pair_candidates, pair_rejected added at the end of the stats; 5: paired_merges
+#define GBPE_ABI_VERSION 7   /* 7: gbpe_encode_batch, gbpe_encode_batch_device (many documents in one call);
+                                 6: pair_candidates, pair_rejected added at the end of the stats; 5: paired_merges
                                  added to the stats, gbpe_ctx_trim (round 6); 4: the late-loop stats removed,
                                  trainer creation time added (round 5) */
 
@@ -314,7 +315,27 @@ int gbpe_encode(gbpe_ctx* ctx, gbpe_trie* trie, const uint8_t* bytes, uint64_t n
 /* Device-resident variant: d_bytes / d_out are device pointers (bench path). */
 int gbpe_encode_device(gbpe_ctx* ctx, gbpe_trie* trie, const void* d_bytes, uint64_t n, uint32_t chunk_size,
                        void* d_out, uint64_t out_cap, uint64_t* n_out);
-/* device ms of the last encode's kernels (walk, scan, compact) */
+/* Many documents in one call (no reference counterpart: tokenizer.js encodes one
+ * buffer at a time).  The documents lie end to end in `bytes`; doc_off has
+ * n_docs + 1 non-decreasing entries, doc_off[0] == 0 and doc_off[n_docs] == n, and
+ * document d is bytes[doc_off[d] .. doc_off[d+1]) (empty documents allowed).
+ * out receives every document's tokens in order and tok_off (n_docs + 1 entries)
+ * their boundaries: out[tok_off[d] .. tok_off[d+1]) is exactly what gbpe_encode
+ * returns for document d alone with the same chunk_size (at most 2^31) — chunks
+ * start at multiples of the chunk size from the document's first byte and no token
+ * crosses a document boundary.  On GBPE_E_CAPACITY *n_out holds the required token
+ * count, tok_off is complete and nothing is written at or beyond out[out_cap].
+ * n_docs == 0 or n == 0: GBPE_OK, *n_out = 0, every tok_off entry 0.
+ * Bad offsets: GBPE_E_INVALID (checked on the host before anything is launched). */
+int gbpe_encode_batch(gbpe_ctx* ctx, gbpe_trie* trie, const uint8_t* bytes, uint64_t n, const uint64_t* doc_off,
+                      uint64_t n_docs, uint32_t chunk_size, uint32_t* out, uint64_t out_cap, uint64_t* tok_off,
+                      uint64_t* n_out);
+/* Device-resident variant: d_bytes (16-byte aligned), d_doc_off and d_tok_off (u64,
+ * 8-byte aligned) and d_out are device pointers.  The offsets are checked by the
+ * first kernel; bad offsets return GBPE_E_INVALID before any other kernel runs. */
+int gbpe_encode_batch_device(gbpe_ctx* ctx, gbpe_trie* trie, const void* d_bytes, uint64_t n, const void* d_doc_off,
+                             uint64_t n_docs, uint32_t chunk_size, void* d_out, uint64_t out_cap, void* d_tok_off,
+                             uint64_t* n_out);
 /* ── merge-rank encode: TokenizerManager.encode (tokenizer-manager.js:13-61) ──
  * merges = [a, b, newId] x n in learned order.  Exact for any merge list: a
  * merge whose operand is only created later never fires (as in the reference). */
@@ -324,6 +345,10 @@ int  gbpe_bpe_encode(gbpe_ctx* ctx, gbpe_bpe* bpe, const uint8_t* bytes, uint64_
                      uint64_t* n_out);
 void gbpe_bpe_free(gbpe_bpe* bpe);
 
+/* device ms of the last encode's kernels (walk, scan, compact); after a batch call:
+ * the walk, every scan and table kernel (document table, descriptors, count scan),
+ * the compaction with the document token offsets (the last group's, when the host
+ * variant ran several) */
 int gbpe_encode_last_timing(gbpe_ctx* ctx, double* ms_walk, double* ms_scan, double* ms_compact);
 
 /* ── device memory helpers for device-resident callers ─────────────────── */
