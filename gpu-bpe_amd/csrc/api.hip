@@ -62,10 +62,15 @@ static void pool_release(GbpePool& pl, bool host, uint64_t keep) {
 }
 
 // GBPE_DEBUG poison=1: every pool block handed out is filled with 0xA5 first (tests:
-// no trainer buffer may rely on a fresh allocation's contents)
-static void pool_poison(gbpe_ctx* ctx, void* p, uint64_t cls, bool host) {
+// no trainer buffer may rely on a fresh allocation's contents), and gbpe_ctx_destroy
+// reports the blocks nobody gave back
+static bool pool_debug() {
     static const bool on = gbpe_debug_knob("poison", 0) != 0;
-    if (!on) return;
+    return on;
+}
+
+static void pool_poison(gbpe_ctx* ctx, void* p, uint64_t cls, bool host) {
+    if (!pool_debug()) return;
     if (host) memset(p, 0xA5, cls);
     else (void)hipMemsetAsync(p, 0xA5, cls, ctx->stream);
 }
@@ -193,6 +198,9 @@ void gbpe_ctx_destroy(gbpe_ctx* ctx) {
     hipFree(ctx->enc_docs);
     hipFree(ctx->pt_agg);
     if (ctx->enc_host_total) hipHostFree(ctx->enc_host_total);
+    if (pool_debug())
+        fprintf(stderr, "[pool] busy at context destroy: device %zu pinned %zu\n", ctx->dpool.busy.size(),
+                ctx->hpool.busy.size());
     gbpe_pool_trim(ctx);   // (blocks still busy belong to trainers the caller did not destroy)
     for (auto& ev : ctx->ev)
         if (ev) hipEventDestroy(ev);

@@ -9,7 +9,9 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "../../include/gpubpe.h"
@@ -59,12 +61,56 @@ void gbpe_pool_trim(gbpe_ctx* ctx);
 hipError_t gbpe_dev_malloc(gbpe_ctx* ctx, void** p, uint64_t bytes);   // hipMalloc, trimming the pool on OOM
 template <typename T>
 inline hipError_t dev_malloc(gbpe_ctx* c, T** p, uint64_t n) { return gbpe_dev_malloc(c, (void**)p, n); }
-template <typename T>
-inline hipError_t pool_malloc(gbpe_ctx* c, T** p, uint64_t n) { return gbpe_pool_alloc(c, (void**)p, n); }
-inline void pool_free(gbpe_ctx* c, void* p) { gbpe_pool_free(c, p); }
-template <typename T>
-inline hipError_t pool_hmalloc(gbpe_ctx* c, T** p, uint64_t n) { return gbpe_pool_alloc(c, (void**)p, n, true); }
-inline void pool_hfree(gbpe_ctx* c, void* p) { gbpe_pool_free(c, p, true); }
+
+// One block of the context pool, owned: `cap` elements at `p` (device, or pinned
+// host with HOST), given back by the destructor.  Move-only.  An untyped array
+// (T = void: the symbol type is chosen at run time) passes its element size to
+// reserve / reserve_keep and keeps `cap` in those elements.
+template <typename T, bool HOST = false>
+struct GbpeArray {
+    gbpe_ctx* ctx = nullptr;
+    T* p = nullptr;
+    uint64_t cap = 0;
+    static constexpr uint64_t ESZ = sizeof(typename std::conditional<std::is_void<T>::value, char, T>::type);
+
+    GbpeArray() = default;
+    GbpeArray(GbpeArray&& o) noexcept : ctx(o.ctx), p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    GbpeArray& operator=(GbpeArray&& o) noexcept {
+        if (this != &o) {
+            release();
+            ctx = o.ctx, p = o.p, cap = o.cap;
+            o.p = nullptr, o.cap = 0;
+        }
+        return *this;
+    }
+    ~GbpeArray() { release(); }
+    T* operator->() const { return p; }
+
+    void release() {
+        if (p) gbpe_pool_free(ctx, p, HOST);
+        p = nullptr, cap = 0;
+    }
+    // room for n elements; the old contents are thrown away when the block has to grow
+    hipError_t reserve(gbpe_ctx* c, uint64_t n, uint64_t esz = ESZ) {
+        if (p && cap >= n) return hipSuccess;
+        release();
+        ctx = c;
+        const hipError_t e = gbpe_pool_alloc(c, (void**)&p, n * esz, HOST);
+        if (e == hipSuccess) cap = n;
+        return e;
+    }
+    // room for n elements with the first `keep` kept: copied on the stream, one
+    // synchronise, then the old block goes back to the pool
+    hipError_t reserve_keep(gbpe_ctx* c, uint64_t n, uint64_t keep, hipStream_t s, uint64_t esz = ESZ) {
+        if (p && cap >= n) return hipSuccess;
+        GbpeArray nb;
+        hipError_t e = nb.reserve(c, n, esz);
+        if (e == hipSuccess && p && keep) e = hipMemcpyAsync(nb.p, p, keep * esz, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e == hipSuccess) *this = std::move(nb);
+        return e;
+    }
+};
 
 // ── error helpers ──────────────────────────────────────────────────────────
 int gbpe_set_error(gbpe_ctx* ctx, int code, const char* fmt, ...);
@@ -80,15 +126,6 @@ int gbpe_set_error(gbpe_ctx* ctx, int code, const char* fmt, ...);
     } while (0)
 
 #define GBPE_LAUNCH_CHECK(ctx) GBPE_HIP(ctx, hipGetLastError())
-
-// runs `f` when the scope ends (device buffers of a call freed on every return path)
-template <typename F>
-struct GbpeScopeExit {
-    F f;
-    ~GbpeScopeExit() { f(); }
-};
-template <typename F>
-GbpeScopeExit<F> gbpe_scope_exit(F f) { return GbpeScopeExit<F>{f}; }
 
 // ── device helpers ─────────────────────────────────────────────────────────
 __device__ __forceinline__ uint32_t gbpe_fmix32(uint32_t x) {

@@ -33,6 +33,10 @@ constexpr uint32_t SP_CH = 256;      // symbols per wave pass over a sector (4 p
 constexpr uint32_t SP_INV = 0xFFFFFFFFu;
 constexpr uint32_t SP_SHRINKS = 64;  // zone shrinks per sparse entry the first sector capacity allows for (sp_reserve grows it)
 constexpr uint32_t SP_SHRINKS_MAX = 1024;   // zone shrinks per sparse entry
+constexpr uint32_t SP_SECW = 256;        // sector window (symbols)
+constexpr uint32_t SP_DIV = 64;          // without the lexicon: enter when last_mc * SP_DIV <= n
+constexpr uint32_t SP_SHRINK_PCT = 200;  // shrink once the zone exceeds SP_SHRINK_PCT % of the target + 4096
+constexpr uint32_t SP_ZONE_F = 3;        // single-GPU zone rule factor (sel_inline, >= 3)
 
 // Per-sector pair signature: a 2048-bit Bloom filter (3 hash bits) of every pair
 // the sector has held since the filters were last rebuilt.  The token bitmap
@@ -755,7 +759,7 @@ __device__ __forceinline__ void zone_seg(DevState* st, DevState* zst, const DevS
 // step counters move on in k_refresh (finish == 2), so nothing a workgroup reads
 // here changes under it.  Saves the k_select launch per merge.
 struct SelShard {
-    uint32_t zf = 3;         // zone rule: z >= max(2 mc + mc_prev, zf mc) + 2 (trainer zone_f)
+    uint32_t zf = SP_ZONE_F; // zone rule: z >= max(2 mc + mc_prev, zf mc) + 2
     uint32_t sub = 1;        // k_body workgroups per bitmap word (1, 2, 4: a row of few words, body_grid)
     uint32_t k2 = 0;         // paired launches allowed (the zone_one form: zone_two)
     uint32_t prej = 0;       // tests (GBPE_DEBUG prej): zone_two's verdict also rejects candidate c when

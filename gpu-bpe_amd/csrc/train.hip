@@ -65,12 +65,18 @@ int trainer_create_impl(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, const u
     const uint64_t ntiles0 = gbpe_div_up(n + cap_extra, TILE);
     t->cap_syms = (ntiles0 + 1) * TILE;
     for (int k = 0; k < 2; ++k) {
-        if (pool_malloc(t->ctx, &t->buf[k], t->cap_syms * t->bps) != hipSuccess)
+        if (t->buf[k].reserve(ctx, t->cap_syms, t->bps) != hipSuccess)
             return fail(gbpe_set_error(ctx, GBPE_E_OOM, "hipMalloc(symbols) failed"));
         // both ping-pong buffers start zeroed, as WebGPU zero-initialises buffers
-        if (hipMemsetAsync(t->buf[k], 0, t->cap_syms * t->bps, s) != hipSuccess)
+        if (hipMemsetAsync(t->buf[k].p, 0, t->cap_syms * t->bps, s) != hipSuccess)
             return fail(gbpe_set_error(ctx, GBPE_E_DEVICE, "memset failed"));
     }
+    if (t->hitmask.reserve(ctx, (ntiles0 + 1) * TPB) != hipSuccess || t->tile_cnt.reserve(ctx, ntiles0 + 1) != hipSuccess ||
+        t->grpsum.reserve(ctx, (ntiles0 / GRP + 2) * GSTR) != hipSuccess || t->st.reserve(ctx, 1) != hipSuccess ||
+        t->d_log.reserve(ctx, (size_t)t->batch * 4) != hipSuccess)
+        return fail(gbpe_set_error(ctx, GBPE_E_OOM, "hipMalloc(training buffers) failed"));
+    if (t->h_st.reserve(ctx, 1) != hipSuccess || t->h_log.reserve(ctx, (size_t)t->batch * 4) != hipSuccess)
+        return fail(gbpe_set_error(ctx, GBPE_E_OOM, "hipHostMalloc failed"));
     // pair table
     // distinct pairs start below 65536 (byte pairs) and grow by a few per merge
     // (1 GiB English at 32K: 170K live, 243K slots used): start at 2^20 slots and
@@ -82,30 +88,11 @@ int trainer_create_impl(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, const u
     if (lg == 0) lg = 20;
     if (lg < BLK_LOG2 + 1) lg = BLK_LOG2 + 1;
     if (lg > 28) lg = 28;
-    t->table_log2 = lg;
-    const uint64_t slots = 1ull << lg;
-    t->tb.mask = (uint32_t)(slots - 1);
-    t->tb.nblk = (uint32_t)(slots >> BLK_LOG2);
-    if (pool_malloc(t->ctx, &t->tb.slots, slots * sizeof(uint2)) != hipSuccess ||
-        pool_malloc(t->ctx, &t->tb.bmax, t->tb.nblk * sizeof(uint64_t)) != hipSuccess ||
-        pool_malloc(t->ctx, &t->tb.bmax2, t->tb.nblk * sizeof(uint64_t)) != hipSuccess ||
-        pool_malloc(t->ctx, &t->tb.dirty, t->tb.nblk * sizeof(uint32_t)) != hipSuccess ||
-        pool_malloc(t->ctx, &t->tb.dlist, (t->tb.nblk + 1) * sizeof(uint32_t)) != hipSuccess ||
-        pool_malloc(t->ctx, &t->tb.blive, t->tb.nblk * sizeof(uint32_t)) != hipSuccess ||
-        pool_malloc(t->ctx, &t->hitmask, (ntiles0 + 1) * TPB * sizeof(uint32_t)) != hipSuccess ||
-        pool_malloc(t->ctx, &t->tile_cnt, (ntiles0 + 1) * sizeof(uint32_t)) != hipSuccess ||
-        pool_malloc(t->ctx, &t->grpsum, (ntiles0 / GRP + 2) * GSTR * sizeof(uint32_t)) != hipSuccess ||
-        pool_malloc(t->ctx, &t->st, sizeof(DevState)) != hipSuccess ||
-        pool_malloc(t->ctx, &t->d_log, (size_t)t->batch * 4 * sizeof(uint32_t)) != hipSuccess)
-        return fail(gbpe_set_error(ctx, GBPE_E_OOM, "hipMalloc(training buffers) failed"));
-    if (pool_hmalloc(t->ctx, &t->h_st, sizeof(DevState)) != hipSuccess ||
-        pool_hmalloc(t->ctx, &t->h_log, (size_t)t->batch * 4 * sizeof(uint32_t)) != hipSuccess)
-        return fail(gbpe_set_error(ctx, GBPE_E_OOM, "hipHostMalloc failed"));
-    t->tb.used = &t->st->used;
-    t->g_refresh = grid_blocks(ctx, t->tb.nblk, 2);
-    if (t->refresh_blocks) t->g_refresh = std::max<uint32_t>(t->refresh_blocks, (uint32_t)gbpe_div_up(t->tb.nblk, 64));
-    if (hipMemsetAsync(t->tb.dirty, 0, t->tb.nblk * sizeof(uint32_t), s) != hipSuccess ||
-        hipMemsetAsync(t->hitmask, 0, (ntiles0 + 1) * TPB * sizeof(uint32_t), s) != hipSuccess)
+    {
+        int rc = table_resize(t, lg);
+        if (rc != GBPE_OK) return fail(rc);
+    }
+    if (hipMemsetAsync(t->hitmask.p, 0, (ntiles0 + 1) * TPB * sizeof(uint32_t), s) != hipSuccess)
         return fail(gbpe_set_error(ctx, GBPE_E_DEVICE, "memset failed"));
     DevState init{};
     init.n = (uint32_t)n;
@@ -115,8 +102,8 @@ int trainer_create_impl(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, const u
         t->last_mc = init.mc;
         t->n_prev0 = si->n_prev;
     }
-    memcpy(t->h_st, &init, sizeof(init));
-    if (hipMemcpyAsync(t->st, t->h_st, sizeof(DevState), hipMemcpyHostToDevice, s) != hipSuccess)
+    memcpy(t->h_st.p, &init, sizeof(init));
+    if (hipMemcpyAsync(t->st.p, t->h_st.p, sizeof(DevState), hipMemcpyHostToDevice, s) != hipSuccess)
         return fail(gbpe_set_error(ctx, GBPE_E_DEVICE, "state upload failed"));
     auto finish = [&]() -> int {
         if (t->flags & GBPE_TRAIN_TIMING) {
@@ -132,16 +119,14 @@ int trainer_create_impl(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, const u
     if (si) {   // both ping-pong buffers from u32 streams (host or device resident)
         const uint32_t* d_cur = (const uint32_t*)bytes;
         const uint32_t* d_prev = si->prev;
-        void* tmp = nullptr;
+        GbpeArray<uint32_t> tmp;
         if (!input_on_device) {
-            if (pool_malloc(t->ctx, &tmp, (n + si->n_prev) * 4 + 4) != hipSuccess)
+            if (tmp.reserve(ctx, n + si->n_prev + 1) != hipSuccess)
                 return fail(gbpe_set_error(ctx, GBPE_E_OOM, "hipMalloc(state) failed"));
-            uint32_t* h = (uint32_t*)tmp;
+            uint32_t* h = tmp.p;
             if (hipMemcpyAsync(h, bytes, n * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
-                (si->n_prev && hipMemcpyAsync(h + n, si->prev, si->n_prev * 4, hipMemcpyHostToDevice, s) != hipSuccess)) {
-                pool_free(t->ctx, tmp);
+                (si->n_prev && hipMemcpyAsync(h + n, si->prev, si->n_prev * 4, hipMemcpyHostToDevice, s) != hipSuccess))
                 return fail(gbpe_set_error(ctx, GBPE_E_DEVICE, "state upload failed"));
-            }
             d_cur = h;
             d_prev = h + n;
         }
@@ -153,63 +138,50 @@ int trainer_create_impl(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, const u
             else
                 hipLaunchKernelGGL(k_import_symbols<uint32_t>, dim3(g), dim3(TPB), 0, s, src, (uint32_t*)dst, cnt);
         };
-        imp(d_cur, t->buf[0], n);
-        if (d_prev) imp(d_prev, t->buf[1], si->n_prev);
+        imp(d_cur, t->buf[0].p, n);
+        if (d_prev) imp(d_prev, t->buf[1].p, si->n_prev);
         const bool launched = hipGetLastError() == hipSuccess;
         int rc = launched ? table_rebuild(t) : gbpe_set_error(ctx, GBPE_E_DEVICE, "symbol import launch failed");
-        hipStreamSynchronize(s);
-        pool_free(t->ctx, tmp);
+        hipStreamSynchronize(s);   // (tmp goes back to the pool)
         if (rc != GBPE_OK) return fail(rc);
         return finish();
     }
     // symbols: bytes (+ mask) → S with word-start bit; input may be host or device resident
     const uint8_t* d_bytes = bytes;
     const uint8_t* d_ws = word_starts;
-    void* tmp = nullptr;
+    GbpeArray<uint8_t> tmp;
     if (!input_on_device) {
-        const uint64_t need = n * (word_starts ? 2 : 1);
-        if (pool_malloc(t->ctx, &tmp, need) != hipSuccess) return fail(gbpe_set_error(ctx, GBPE_E_OOM, "hipMalloc(input) failed"));
-        if (hipMemcpyAsync(tmp, bytes, n, hipMemcpyHostToDevice, s) != hipSuccess ||
-            (word_starts && hipMemcpyAsync((uint8_t*)tmp + n, word_starts, n, hipMemcpyHostToDevice, s) != hipSuccess)) {
-            pool_free(t->ctx, tmp);
+        if (tmp.reserve(ctx, n * (word_starts ? 2 : 1)) != hipSuccess)
+            return fail(gbpe_set_error(ctx, GBPE_E_OOM, "hipMalloc(input) failed"));
+        if (hipMemcpyAsync(tmp.p, bytes, n, hipMemcpyHostToDevice, s) != hipSuccess ||
+            (word_starts && hipMemcpyAsync(tmp.p + n, word_starts, n, hipMemcpyHostToDevice, s) != hipSuccess))
             return fail(gbpe_set_error(ctx, GBPE_E_DEVICE, "input upload failed"));
-        }
-        d_bytes = (const uint8_t*)tmp;
-        d_ws = word_starts ? (const uint8_t*)tmp + n : nullptr;
+        d_bytes = tmp.p;
+        d_ws = word_starts ? tmp.p + n : nullptr;
     }
-    uint8_t* d_gpt4 = nullptr;   // GPT-4 rule word starts computed on the device (pre_tokenizer.mjs:226-292)
+    GbpeArray<uint8_t> d_gpt4;   // GPT-4 rule word starts computed on the device (pre_tokenizer.mjs:226-292)
     if (!d_ws && (opts->flags & GBPE_TRAIN_GPT4_BOUNDARIES)) {
-        int rc2 = pool_malloc(t->ctx, &d_gpt4, n) == hipSuccess ? gbpe_pretok_gpt4_launch(ctx, d_bytes, n, d_gpt4) : GBPE_E_OOM;
-        if (rc2 != GBPE_OK) {
-            if (tmp) pool_free(t->ctx, tmp);
-            pool_free(t->ctx, d_gpt4);
-            return fail(rc2 == GBPE_E_OOM ? gbpe_set_error(ctx, GBPE_E_OOM, "hipMalloc(word starts) failed") : rc2);
-        }
-        d_ws = d_gpt4;
+        if (d_gpt4.reserve(ctx, n) != hipSuccess) return fail(gbpe_set_error(ctx, GBPE_E_OOM, "hipMalloc(word starts) failed"));
+        int rc2 = gbpe_pretok_gpt4_launch(ctx, d_bytes, n, d_gpt4.p);
+        if (rc2 != GBPE_OK) return fail(rc2);
+        d_ws = d_gpt4.p;
     }
     const uint32_t gb = (uint32_t)gbpe_div_up(n, TPB);
     const bool vec = ((uintptr_t)d_bytes & 15u) == 0 && ((uintptr_t)d_ws & 15u) == 0;   // (null is aligned)
     const uint32_t gv = (uint32_t)gbpe_div_up(gbpe_div_up(n, 16), TPB);
     if (t->u16 && vec)
-        hipLaunchKernelGGL(k_symbols_v<uint16_t>, dim3(gv), dim3(TPB), 0, s, d_bytes, d_ws, (uint16_t*)t->buf[0], n);
+        hipLaunchKernelGGL(k_symbols_v<uint16_t>, dim3(gv), dim3(TPB), 0, s, d_bytes, d_ws, (uint16_t*)t->buf[0].p, n);
     else if (vec)
-        hipLaunchKernelGGL(k_symbols_v<uint32_t>, dim3(gv), dim3(TPB), 0, s, d_bytes, d_ws, (uint32_t*)t->buf[0], n);
+        hipLaunchKernelGGL(k_symbols_v<uint32_t>, dim3(gv), dim3(TPB), 0, s, d_bytes, d_ws, (uint32_t*)t->buf[0].p, n);
     else if (t->u16)
-        hipLaunchKernelGGL(k_symbols<uint16_t>, dim3(gb), dim3(TPB), 0, s, d_bytes, d_ws, (uint16_t*)t->buf[0], n,
+        hipLaunchKernelGGL(k_symbols<uint16_t>, dim3(gb), dim3(TPB), 0, s, d_bytes, d_ws, (uint16_t*)t->buf[0].p, n,
                            (uint8_t*)nullptr);
     else
-        hipLaunchKernelGGL(k_symbols<uint32_t>, dim3(gb), dim3(TPB), 0, s, d_bytes, d_ws, (uint32_t*)t->buf[0], n,
+        hipLaunchKernelGGL(k_symbols<uint32_t>, dim3(gb), dim3(TPB), 0, s, d_bytes, d_ws, (uint32_t*)t->buf[0].p, n,
                            (uint8_t*)nullptr);
-    if (hipGetLastError() != hipSuccess) {
-        if (tmp) pool_free(t->ctx, tmp);
-        return fail(gbpe_set_error(ctx, GBPE_E_DEVICE, "symbol kernel launch failed"));
-    }
+    if (hipGetLastError() != hipSuccess) return fail(gbpe_set_error(ctx, GBPE_E_DEVICE, "symbol kernel launch failed"));
     int rc = table_rebuild(t, true);
-    if (tmp || d_gpt4) {
-        hipStreamSynchronize(s);
-        pool_free(t->ctx, tmp);
-        pool_free(t->ctx, d_gpt4);
-    }
+    if (tmp.p || d_gpt4.p) hipStreamSynchronize(s);   // (before they go back to the pool)
     if (rc != GBPE_OK) return fail(rc);
     return finish();
 }
@@ -265,20 +237,20 @@ int trainer_step_once(gbpe_trainer* t, uint32_t max_merges, uint32_t* merges_out
         // with the word lexicon the body costs what its distinct words cost, so the
         // loop can enter as soon as the zone (~7 x the next count) is a small part of
         // the stream — before the first merge; without it, once counts
-        // are a 1/sp_div fraction
+        // are a 1/SP_DIV fraction
         // with the lexicon the decision (and the zone) follow the NEXT merge's count,
         // the table maximum: one huge first merge (C5's (32,32), 17 % of the stream)
         // then ends only a one-merge dense step (enter_lim below)
         uint32_t mc = t->last_mc, next = 0;
         if (t->lex_on) {
-            if (!t->d_u32) TR_HIP(t, pool_malloc(t->ctx, &t->d_u32, 64));
-            hipLaunchKernelGGL(k_topcount, dim3(1), dim3(1024), 0, s, t->tb, t->d_u32);
+            TR_HIP(t, t->d_u32.reserve(t->ctx, 16));
+            hipLaunchKernelGGL(k_topcount, dim3(1), dim3(1024), 0, s, t->tb, t->d_u32.p);
             GBPE_LAUNCH_CHECK(t->ctx);
-            TR_HIP(t, hipMemcpyAsync(&next, t->d_u32, 4, hipMemcpyDeviceToHost, s));
+            TR_HIP(t, hipMemcpyAsync(&next, t->d_u32.p, 4, hipMemcpyDeviceToHost, s));
             TR_HIP(t, hipStreamSynchronize(s));
             mc = next;
         }
-        const uint64_t div = t->lex_on ? t->lx_div : t->sp_div;
+        const uint64_t div = t->lex_on ? t->lx_div : SP_DIV;
         const bool count_ok = mc && ((t->flags & GBPE_TRAIN_SPARSE_EARLY) || (uint64_t)mc * div <= t->n);
         if (count_ok) {
             int rc = t->u16 ? sp_enter<uint16_t>(t, true, next) : sp_enter<uint32_t>(t, true, next);
@@ -320,17 +292,17 @@ int trainer_step_once(gbpe_trainer* t, uint32_t max_merges, uint32_t* merges_out
     // a large zone shrinks every sub_k merges instead of every step (early counts fall fast)
     if (t->sp && (uint32_t)t->n - t->h_st->B > t->sub_zone && k > t->sub_k) k = t->sub_k;
     // reset the per-step counter + budget (trainer.js:239)
-    DevState* hs = t->h_st;
+    DevState* hs = t->h_st.p;
     hs->merges_done = 0;
     hs->budget = k;
     if (t->sp) hs->sel_round = 0;
-    hipLaunchKernelGGL(k_step_in, dim3(1), dim3(1), 0, s, t->st, t->sp ? t->zst : (DevState*)nullptr, k);
+    hipLaunchKernelGGL(k_step_in, dim3(1), dim3(1), 0, s, t->st.p, t->sp ? t->zst.p : (DevState*)nullptr, k);
 #ifdef GBPE_KTRACE
     if (getenv("GBPE_KTRACE_OUT")) {
         static unsigned long long* kbuf = nullptr;
         if (!kbuf) {
             const size_t nb = (size_t)(KT_MERGES / KT_EVERY) * 2 * KT_WG * KT_SLOTS * 8;
-            TR_HIP(t, pool_malloc(t->ctx, &kbuf, nb));
+            TR_HIP(t, dev_malloc(t->ctx, &kbuf, nb));   // (kept for the process: outside the pool)
             TR_HIP(t, hipMemsetAsync(kbuf, 0, nb, s));
             TR_HIP(t, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_ktr), &kbuf, sizeof(kbuf), 0, hipMemcpyHostToDevice, s));
         }
@@ -354,18 +326,15 @@ int trainer_step_once(gbpe_trainer* t, uint32_t max_merges, uint32_t* merges_out
         const uint32_t z256 = t->u16 ? zone_max<uint16_t>(256) : zone_max<uint32_t>(256);
         sg.bt = zn <= std::min<uint32_t>(z256, t->z256) ? 256 : 1024;   // small zone: the low-latency 256-thread workgroups
         body_grid(t, sg.bt, &sg.body, &sg.wpg, 0, &sg.sub);
-        if (sg.bt == 1024 && t->u16 && zn <= 16384u && t->zone16) sg.bt = 1023;
+        if (sg.bt == 1024 && t->u16 && zn <= 16384u) sg.bt = 1023;
         sg.zone1 = zn <= (t->u16 ? zone_max<uint16_t>(sg.bt) : zone_max<uint32_t>(sg.bt)) ? 1u : 0u;
         // a zone of 16K-1M symbols: 16K-symbol segments inside k_body (its ZSEG form)
-        const uint32_t zs_lo = t->zseg_mode == 2 ? (t->u16 ? zone_max<uint16_t>(1024) : zone_max<uint32_t>(1024)) : t->zseg_lo;
-        if (t->zseg_mode && t->zseg && zn > zs_lo && zn <= NSEG_MAX * 16384u) {
+        if (t->zseg.p && zn > t->zseg_lo && zn <= NSEG_MAX * 16384u) {
             sg.seg8 = t->seg8 && zn <= NSEG_MAX * 8192u;
             sg.zone1 = (uint32_t)gbpe_div_up(zn, sg.seg8 ? 8192u : 16384u);
         }
         sg.copy = (t->flags & GBPE_TRAIN_EXACT_COMPACTION) ? 0u : grid_persistent(t->ctx, gbpe_div_up(zn / 5 + 1, TPB * 8), 1);
         sg.zdelta = (uint32_t)(zt ? zt : 1);
-        sg.ztail = (t->flags & GBPE_TRAIN_EXACT_COMPACTION) ? 0u
-                                                           : (uint32_t)std::min<uint64_t>(1024, gbpe_div_up(zn / 5 + 1, 2048));
         sg.zcompact = (uint32_t)zt + ((t->flags & GBPE_TRAIN_EXACT_COMPACTION) ? 0u
                                       : grid_persistent(t->ctx, gbpe_div_up(zn / 2 + 1, TPB * 16), 1));
         // the 1024-thread forms hold one workgroup per CU (their LDS): the zone's (or
@@ -387,20 +356,20 @@ int trainer_step_once(gbpe_trainer* t, uint32_t max_merges, uint32_t* merges_out
             if (want != t->g_refresh) {
                 t->g_refresh = g_refresh = want;
                 if (t->u16)
-                    GBPE_LAUNCH_REFRESH(uint16_t, want, t->tb.nblk, s, t->st, 0u, 0, t->tb, (uint16_t*)nullptr,
+                    GBPE_LAUNCH_REFRESH(uint16_t, want, t->tb.nblk, s, t->st.p, 0u, 0, t->tb, (uint16_t*)nullptr,
                                         (const uint32_t*)nullptr, (DevState*)nullptr, (uint32_t*)nullptr, FusedSel(),
-                                        t->part, (uint32_t*)nullptr);
+                                        t->part.p, (uint32_t*)nullptr);
                 else
-                    GBPE_LAUNCH_REFRESH(uint32_t, want, t->tb.nblk, s, t->st, 0u, 0, t->tb, (uint32_t*)nullptr,
+                    GBPE_LAUNCH_REFRESH(uint32_t, want, t->tb.nblk, s, t->st.p, 0u, 0, t->tb, (uint32_t*)nullptr,
                                         (const uint32_t*)nullptr, (DevState*)nullptr, (uint32_t*)nullptr, FusedSel(),
-                                        t->part, (uint32_t*)nullptr);
+                                        t->part.p, (uint32_t*)nullptr);
                 GBPE_LAUNCH_CHECK(t->ctx);
             }
         }
         sg.refresh = g_refresh;
         // paired launches: the late zone_one form, two merges per launch
         // when the table's top two allow it
-        sg.pair = t->pair_on && sg.zone1 == 1 && sg.bt == 256 && t->zseg && k >= 2;
+        sg.pair = t->pair_on && sg.zone1 == 1 && sg.bt == 256 && t->zseg.p && k >= 2;
     }
     // a paired step needs fewer launches than merges: sized by the last paired step's
     // rate (+2); launches past the step's budget are no-ops, and a step whose launches
@@ -429,10 +398,10 @@ int trainer_step_once(gbpe_trainer* t, uint32_t max_merges, uint32_t* merges_out
         if (rc != GBPE_OK) return rc;
         h1 = std::chrono::steady_clock::now();
         // the read-backs (and, sparse, k_live's count) in one launch: no copy blits
-        const bool cl = sparse && t->d_clog;
-        hipLaunchKernelGGL(k_step_out, dim3(1), dim3(1024), 0, s, t->st, sparse ? t->zst : (DevState*)nullptr, t->tb,
-                           sparse ? 1 : 0, (const uint32_t*)t->d_log, k * 4u, (const uint32_t*)(cl ? t->d_clog : nullptr),
-                           cl ? k * 2u : 0u, t->h_st, t->h_zst, t->h_log, cl ? t->h_clog : (uint32_t*)nullptr);
+        const bool cl = sparse && t->d_clog.p;
+        hipLaunchKernelGGL(k_step_out, dim3(1), dim3(1024), 0, s, t->st.p, sparse ? t->zst.p : (DevState*)nullptr, t->tb,
+                           sparse ? 1 : 0, (const uint32_t*)t->d_log.p, k * 4u, (const uint32_t*)(cl ? t->d_clog.p : nullptr),
+                           cl ? k * 2u : 0u, t->h_st.p, t->h_zst.p, t->h_log.p, cl ? t->h_clog.p : (uint32_t*)nullptr);
         GBPE_LAUNCH_CHECK(t->ctx);
     }
     TR_HIP(t, hipStreamSynchronize(s));
@@ -444,7 +413,7 @@ int trainer_step_once(gbpe_trainer* t, uint32_t max_merges, uint32_t* merges_out
         if (t->ptrace)   // (diagnostic, GBPE_DEBUG ptrace=1) the step's form and pairing
             fprintf(stderr, "[ptrace] merge %u zone %u zone1 %u bt %d pair %d launches %u done %u paired %u cand %u mc %u us %.1f\n",
                     t->done, hs->n - hs->B, sg.zone1, sg.bt, sg.pair ? 1 : 0, nl, done, dbl,
-                    hs->pair_cand, done ? t->h_log[(done - 1) * 4 + 3] : 0u,
+                    hs->pair_cand, done ? t->h_log.p[(done - 1) * 4 + 3] : 0u,
                     std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - hs0).count());
     }
     if (t->htime) {   // (diagnostic) host enqueue vs wait; "late": a zone of <= 16K symbols
@@ -505,22 +474,22 @@ int trainer_step_once(gbpe_trainer* t, uint32_t max_merges, uint32_t* merges_out
     // algorithmic stream bytes: s * (2 N_i + N_{i+1})
     uint64_t N = t->n;
     for (uint32_t r = 0; r < done; ++r) {
-        const uint64_t mc = t->h_log[r * 4 + 3];
+        const uint64_t mc = t->h_log.p[r * 4 + 3];
         t->bytes_moved += (uint64_t)t->bps * (2 * N + (N - mc));
         if (!sparse) t->dense_bytes += (uint64_t)t->bps * (2 * N + (N - mc));
         N -= mc;
-        if (merges_out) memcpy(merges_out + 4 * r, t->h_log + 4 * r, 4 * sizeof(uint32_t));
+        if (merges_out) memcpy(merges_out + 4 * r, t->h_log.p + 4 * r, 4 * sizeof(uint32_t));
     }
     if ((uint32_t)N != hs->n) return gbpe_set_error(t->ctx, GBPE_E_INTERNAL, "host/device symbol count disagree");
     t->n = N;
-    if (done) t->last_mc = t->h_log[(done - 1) * 4 + 3];
+    if (done) t->last_mc = t->h_log.p[(done - 1) * 4 + 3];
     if (t->trace) {   // merge index, count, stream length before, sparse, candidate sectors, sectors with sites
         uint64_t nn = N;
-        for (uint32_t r = done; r-- > 0;) nn += t->h_log[r * 4 + 3];
+        for (uint32_t r = done; r-- > 0;) nn += t->h_log.p[r * 4 + 3];
         for (uint32_t r = 0; r < done; ++r) {
-            fprintf(t->trace, "%u %u %llu %d %u %u\n", t->done + r, t->h_log[r * 4 + 3], (unsigned long long)nn,
-                    sparse ? 1 : 0, sparse && t->h_clog ? t->h_clog[2 * r] : 0u, sparse && t->h_clog ? t->h_clog[2 * r + 1] : 0u);
-            nn -= t->h_log[r * 4 + 3];
+            fprintf(t->trace, "%u %u %llu %d %u %u\n", t->done + r, t->h_log.p[r * 4 + 3], (unsigned long long)nn,
+                    sparse ? 1 : 0, sparse && t->h_clog.p ? t->h_clog.p[2 * r] : 0u, sparse && t->h_clog.p ? t->h_clog.p[2 * r + 1] : 0u);
+            nn -= t->h_log.p[r * 4 + 3];
         }
     }
     if (sparse) {
@@ -609,9 +578,9 @@ extern "C" int gbpe_trainer_stats_get(gbpe_trainer* t, gbpe_trainer_stats* o) {
     o->lexicon_words = t->lx_words;
     o->lexicon_entries = t->lx_nuid;
     o->lexicon_symbols = t->lx_len;
-    if (t->wg_bytes && t->wg_cap) {   // the per-workgroup counters of k_body (and its zone workgroup)
-        std::vector<uint64_t> h(t->wg_cap);
-        if (hipMemcpy(h.data(), t->wg_bytes, t->wg_cap * sizeof(uint64_t), hipMemcpyDeviceToHost) == hipSuccess)
+    if (t->wg_bytes.p) {   // the per-workgroup counters of k_body (and its zone workgroup)
+        std::vector<uint64_t> h(t->wg_bytes.cap);
+        if (hipMemcpy(h.data(), t->wg_bytes.p, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost) == hipSuccess)
             for (uint64_t v : h) o->body_bytes += v;
     }
     return GBPE_OK;
@@ -627,20 +596,19 @@ extern "C" int gbpe_trainer_symbols(gbpe_trainer* t, uint32_t* out, uint64_t cap
         if (rc != GBPE_OK) return rc;
     }
     hipStream_t s = t->ctx->stream;
-    uint32_t* d = nullptr;
-    TR_HIP(t, pool_malloc(t->ctx, &d, (uint64_t)t->n * 4 + 4));
+    GbpeArray<uint32_t> d;
+    TR_HIP(t, d.reserve(t->ctx, t->n + 1));
     const uint32_t g = (uint32_t)gbpe_div_up(t->n, 256);
     if (t->n) {
         if (t->u16)
-            hipLaunchKernelGGL(k_export_symbols<uint16_t>, dim3(g), dim3(256), 0, s, (const uint16_t*)t->buf[t->cur], d,
+            hipLaunchKernelGGL(k_export_symbols<uint16_t>, dim3(g), dim3(256), 0, s, (const uint16_t*)t->buf[t->cur].p, d.p,
                                (uint64_t)t->n);
         else
-            hipLaunchKernelGGL(k_export_symbols<uint32_t>, dim3(g), dim3(256), 0, s, (const uint32_t*)t->buf[t->cur], d,
+            hipLaunchKernelGGL(k_export_symbols<uint32_t>, dim3(g), dim3(256), 0, s, (const uint32_t*)t->buf[t->cur].p, d.p,
                                (uint64_t)t->n);
     }
-    hipError_t e = hipMemcpyAsync(out, d, (uint64_t)t->n * 4, hipMemcpyDeviceToHost, s);
+    hipError_t e = hipMemcpyAsync(out, d.p, (uint64_t)t->n * 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    pool_free(t->ctx, d);
     if (e != hipSuccess) return gbpe_set_error(t->ctx, GBPE_E_DEVICE, "symbol export failed: %s", hipGetErrorString(e));
     return GBPE_OK;
 }
@@ -656,7 +624,7 @@ extern "C" int gbpe_trainer_export_state(gbpe_trainer* t, uint32_t* cur, uint64_
         if (rc != GBPE_OK) return rc;
     }
     hipStream_t s = t->ctx->stream;
-    TR_HIP(t, hipMemcpyAsync(t->h_st, t->st, sizeof(DevState), hipMemcpyDeviceToHost, s));
+    TR_HIP(t, hipMemcpyAsync(t->h_st.p, t->st.p, sizeof(DevState), hipMemcpyDeviceToHost, s));
     TR_HIP(t, hipStreamSynchronize(s));
     const uint64_t n = t->n;
     // (a trainer created from a state and not stepped since re-exports the imported length)
@@ -668,8 +636,9 @@ extern "C" int gbpe_trainer_export_state(gbpe_trainer* t, uint32_t* cur, uint64_
     if ((cur && cap_cur < n) || (prev && cap_prev < np))
         return gbpe_set_error(t->ctx, GBPE_E_CAPACITY, "export_state: need %llu + %llu", (unsigned long long)n,
                               (unsigned long long)np);
-    uint32_t* d = nullptr;
-    if (!on_device) TR_HIP(t, pool_malloc(t->ctx, &d, (n + np) * 4 + 4));
+    GbpeArray<uint32_t> stage;
+    if (!on_device) TR_HIP(t, stage.reserve(t->ctx, n + np + 1));
+    uint32_t* d = stage.p;
     auto exp = [&](const void* src, uint32_t* dst, uint64_t cnt) {
         if (!cnt || !dst) return;
         const uint32_t g = (uint32_t)gbpe_div_up(cnt, 256);
@@ -678,15 +647,14 @@ extern "C" int gbpe_trainer_export_state(gbpe_trainer* t, uint32_t* cur, uint64_
         else
             hipLaunchKernelGGL(k_export_symbols<uint32_t>, dim3(g), dim3(256), 0, s, (const uint32_t*)src, dst, cnt);
     };
-    exp(t->buf[t->cur], on_device ? cur : d, n);
-    exp(t->buf[t->cur ^ 1], on_device ? prev : d + n, np);
+    exp(t->buf[t->cur].p, on_device ? cur : d, n);
+    exp(t->buf[t->cur ^ 1].p, on_device ? prev : d + n, np);
     hipError_t e = hipGetLastError();
     if (!on_device) {
         if (e == hipSuccess && cur && n) e = hipMemcpyAsync(cur, d, n * 4, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess && prev && np) e = hipMemcpyAsync(prev, d + n, np * 4, hipMemcpyDeviceToHost, s);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    pool_free(t->ctx, d);
     if (e != hipSuccess) return gbpe_set_error(t->ctx, GBPE_E_DEVICE, "state export failed: %s", hipGetErrorString(e));
     return GBPE_OK;
 }
@@ -694,9 +662,10 @@ extern "C" int gbpe_trainer_export_state(gbpe_trainer* t, uint32_t* cur, uint64_
 extern "C" int gbpe_trainer_pair_counts(gbpe_trainer* t, uint32_t* pids, uint32_t* counts, uint64_t cap, uint64_t* n) {
     if (!t || !n) return GBPE_E_INVALID;
     hipStream_t s = t->ctx->stream;
-    uint32_t* d = nullptr;
+    GbpeArray<uint32_t> own;
     const uint64_t c = cap ? cap : 1;
-    TR_HIP(t, pool_malloc(t->ctx, &d, (2 * c + 1) * sizeof(uint32_t)));
+    TR_HIP(t, own.reserve(t->ctx, 2 * c + 1));
+    uint32_t* d = own.p;
     hipError_t e = hipMemsetAsync(d, 0, sizeof(uint32_t), s);
     const uint64_t slots = (uint64_t)t->tb.mask + 1;
     hipLaunchKernelGGL(k_dump_pairs, dim3((uint32_t)gbpe_div_up(slots, 256)), dim3(256), 0, s, t->tb, d + 1, d + 1 + c,
@@ -708,7 +677,6 @@ extern "C" int gbpe_trainer_pair_counts(gbpe_trainer* t, uint32_t* pids, uint32_
         e = hipMemcpy(pids, d + 1, (uint64_t)cnt * 4, hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = hipMemcpy(counts, d + 1 + c, (uint64_t)cnt * 4, hipMemcpyDeviceToHost);
     }
-    pool_free(t->ctx, d);
     if (e != hipSuccess) return gbpe_set_error(t->ctx, GBPE_E_DEVICE, "pair dump failed: %s", hipGetErrorString(e));
     *n = cnt;
     if (cnt > cap) return gbpe_set_error(t->ctx, GBPE_E_CAPACITY, "pair dump: need %u", cnt);
@@ -718,7 +686,7 @@ extern "C" int gbpe_trainer_pair_counts(gbpe_trainer* t, uint32_t* pids, uint32_
 extern "C" void gbpe_trainer_destroy(gbpe_trainer* t) {
     if (!t) return;
     if (t->ctx && t->ctx->stream) hipStreamSynchronize(t->ctx->stream);
-    if (t->htime && t->h_st)   // paired launches: candidates, window-check rejections, run
+    if (t->htime && t->h_st.p)   // paired launches: candidates, window-check rejections, run
         fprintf(stderr, "[pair] candidates %u rejected %u paired %u\n", t->h_st->pair_cand, t->h_st->pair_rej,
                 t->h_st->paired);
     if (t->htime && t->ht_steps)
@@ -749,47 +717,7 @@ extern "C" void gbpe_trainer_destroy(gbpe_trainer* t) {
 #endif
     for (auto& e : t->evs)
         if (e) hipEventDestroy(e);
-    pool_free(t->ctx, t->buf[0]);
-    pool_free(t->ctx, t->buf[1]);
-    pool_free(t->ctx, t->tb.slots);
-    pool_free(t->ctx, t->tb.bmax);
-    pool_free(t->ctx, t->tb.bmax2);
-    pool_free(t->ctx, t->tb.dirty);
-    pool_free(t->ctx, t->tb.dlist);
-    pool_free(t->ctx, t->tb.blive);
-    pool_free(t->ctx, t->hitmask);
-    pool_free(t->ctx, t->tile_cnt);
-    pool_free(t->ctx, t->grpsum);
-    pool_free(t->ctx, t->sec);
-    pool_free(t->ctx, t->sp_loc);
-    pool_free(t->ctx, t->sp_blk);
-    pool_free(t->ctx, t->bits);
-    pool_free(t->ctx, t->sig);
-    pool_free(t->ctx, t->zbuf[0]);
-    pool_free(t->ctx, t->zbuf[1]);
-    pool_free(t->ctx, t->wtmp);
-    pool_free(t->ctx, t->zst);
-    pool_free(t->ctx, t->d_u32);
-    pool_free(t->ctx, t->part);
-    pool_free(t->ctx, t->d_bhist);
-    pool_free(t->ctx, t->zseg);
-    pool_free(t->ctx, t->zdr_out);
-    pool_free(t->ctx, t->zdr_offs);
-    pool_free(t->ctx, t->zdr_flag);
-    pool_free(t->ctx, t->wg_bytes);
-    pool_free(t->ctx, t->lx_store);
-    pool_free(t->ctx, t->lx_mul);
-    pool_free(t->ctx, t->lx_occ);
-    pool_free(t->ctx, t->lx_w0);
-    pool_free(t->ctx, t->lx_tmp);
-    if (t->h_zst) pool_hfree(t->ctx, t->h_zst);
-    pool_free(t->ctx, t->d_clog);
-    if (t->h_clog) pool_hfree(t->ctx, t->h_clog);
     if (t->trace) fclose(t->trace);
-    pool_free(t->ctx, t->st);
-    pool_free(t->ctx, t->d_log);
-    if (t->h_st) pool_hfree(t->ctx, t->h_st);
-    if (t->h_log) pool_hfree(t->ctx, t->h_log);
     delete t;
 }
 
@@ -842,15 +770,15 @@ extern "C" int gbpe_word_boundary(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t 
     if (!ctx || (!bytes && n) || (!ws_out && n)) return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
     if (n == 0) return GBPE_OK;
     hipStream_t s = ctx->stream;
-    uint8_t* d = nullptr;
-    GBPE_HIP(ctx, pool_malloc(ctx, &d, 2 * n));
+    GbpeArray<uint8_t> own;
+    GBPE_HIP(ctx, own.reserve(ctx, 2 * n));
+    uint8_t* d = own.p;
     hipError_t e = hipMemcpyAsync(d, bytes, n, hipMemcpyHostToDevice, s);
     hipLaunchKernelGGL(k_symbols<uint32_t>, dim3((uint32_t)gbpe_div_up(n, TPB)), dim3(TPB), 0, s, d,
                        (const uint8_t*)nullptr, (uint32_t*)nullptr, n, d + n);
     if (e == hipSuccess) e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(ws_out, d + n, n, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    pool_free(ctx, d);
     if (e != hipSuccess) return gbpe_set_error(ctx, GBPE_E_DEVICE, "word boundary failed: %s", hipGetErrorString(e));
     return GBPE_OK;
 }

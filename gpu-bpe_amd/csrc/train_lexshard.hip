@@ -26,13 +26,13 @@ struct gbpe_lexshard {
     uint32_t bps = 2;
     uint64_t n = 0, Zs = 0, z = 0;
     uint32_t top = 0;            // the piece's largest pair count
-    void* store = nullptr;       // distinct words, each followed by a 0 separator (S layout)
-    uint32_t* mul = nullptr;     // per store symbol: its word's occurrences in the piece
+    GbpeArray<void> store;       // distinct words, each followed by a 0 separator (S layout)
+    GbpeArray<uint32_t> mul;     // per store symbol: its word's occurrences in the piece
     uint64_t T = 0;
-    uint32_t* occ = nullptr;     // the piece's body words in stream order: local uid (global after remap) or LX_LIT
+    GbpeArray<uint32_t> occ;     // the piece's body words in stream order: local uid (global after remap) or LX_LIT
     uint64_t nw = 0;
     uint32_t nu = 0;
-    void* zone = nullptr;        // the piece's zone (last rank): symbols [Zs, n)
+    GbpeArray<void> zone;        // the piece's zone (last rank): symbols [Zs, n)
     bool built = false, remapped = false;
 };
 
@@ -85,15 +85,15 @@ template <typename S>
 int ls_build(gbpe_lexshard* ls, uint64_t zone_target) {
     gbpe_trainer* t = ls->t;
     hipStream_t s = ls->ctx->stream;
-    const S* cur = (const S*)t->buf[t->cur];
+    const S* cur = (const S*)t->buf[t->cur].p;
     const uint64_t n = t->n;
     uint32_t Zs = (uint32_t)n;
     if (zone_target >= n) {   // the whole piece lies inside the zone (a zone spanning several pieces)
         Zs = 0;
     } else if (zone_target) {   // the piece's tail from the last word start at or before n - zone_target
-        hipLaunchKernelGGL(k_sp_zone_start<S>, dim3(1), dim3(1024), 0, s, cur, (uint32_t)(n - zone_target), t->d_u32);
+        hipLaunchKernelGGL(k_sp_zone_start<S>, dim3(1), dim3(1024), 0, s, cur, (uint32_t)(n - zone_target), t->d_u32.p);
         GBPE_LAUNCH_CHECK(ls->ctx);
-        TR_HIP(t, hipMemcpyAsync(&Zs, t->d_u32, 4, hipMemcpyDeviceToHost, s));
+        TR_HIP(t, hipMemcpyAsync(&Zs, t->d_u32.p, 4, hipMemcpyDeviceToHost, s));
         TR_HIP(t, hipStreamSynchronize(s));
     }
     LxPlan lp;
@@ -108,17 +108,17 @@ int ls_build(gbpe_lexshard* ls, uint64_t zone_target) {
     ls->nu = lp.nu;
     ls->nw = lp.nw;
     const uint64_t T = lp.T;
-    if (pool_malloc(ls->ctx, &ls->store, (T + 64) * ls->bps) != hipSuccess ||
-        pool_malloc(ls->ctx, &ls->mul, (T + 64) * 4) != hipSuccess || pool_malloc(ls->ctx, &ls->occ, (lp.nw + 1) * 4) != hipSuccess ||
-        (ls->z && pool_malloc(ls->ctx, &ls->zone, (ls->z + 64) * ls->bps) != hipSuccess))
+    if (ls->store.reserve(ls->ctx, T + 64, ls->bps) != hipSuccess || ls->mul.reserve(ls->ctx, T + 64) != hipSuccess ||
+        ls->occ.reserve(ls->ctx, lp.nw + 1) != hipSuccess ||
+        (ls->z && ls->zone.reserve(ls->ctx, ls->z + 64, ls->bps) != hipSuccess))
         return gbpe_set_error(ls->ctx, GBPE_E_OOM, "lexshard: hipMalloc(store) failed");
     if (lp.nu)
         hipLaunchKernelGGL(k_lx_fill<S>, dim3((uint32_t)gbpe_div_up(lp.nu, 256)), dim3(256), 0, s, cur,
                            (const uint32_t*)lp.urep, (const uint32_t*)lp.usz, (const uint32_t*)lp.umul,
-                           (const uint32_t*)lp.upre, (const uint64_t*)lp.ublk, lp.nu, (S*)ls->store, ls->mul);
+                           (const uint32_t*)lp.upre, (const uint64_t*)lp.ublk, lp.nu, (S*)ls->store.p, ls->mul.p);
     GBPE_LAUNCH_CHECK(ls->ctx);
-    if (lp.nw) TR_HIP(t, hipMemcpyAsync(ls->occ, lp.occ, lp.nw * 4, hipMemcpyDeviceToDevice, s));
-    if (ls->z) TR_HIP(t, hipMemcpyAsync(ls->zone, cur + Zs, ls->z * ls->bps, hipMemcpyDeviceToDevice, s));
+    if (lp.nw) TR_HIP(t, hipMemcpyAsync(ls->occ.p, lp.occ, lp.nw * 4, hipMemcpyDeviceToDevice, s));
+    if (ls->z) TR_HIP(t, hipMemcpyAsync(ls->zone.p, cur + Zs, ls->z * ls->bps, hipMemcpyDeviceToDevice, s));
     TR_HIP(t, hipStreamSynchronize(s));
     ls->built = true;
     return GBPE_OK;
@@ -158,11 +158,11 @@ int lex_root_build(gbpe_trainer* t, const S* store, const uint32_t* mul, uint64_
     *n_map = nent;
     if (nent) {
         hipLaunchKernelGGL(k_lx_map, dim3((uint32_t)gbpe_div_up(nent, 256)), dim3(256), 0, s, (const uint32_t*)lp.occ,
-                           nent, d_map, t->d_u32 + 1);
+                           nent, d_map, t->d_u32.p + 1);
         GBPE_LAUNCH_CHECK(ctx);
     }
     // sectors, bitmap, signatures, store (the body is the deduplicated store)
-    const uint64_t cap = gbpe_div_up((uint64_t)lp.T + z / 16, t->sp_secw) + 2 * (SP_SHRINKS + 1);   // (sp_reserve grows it)
+    const uint64_t cap = gbpe_div_up((uint64_t)lp.T + z / 16, SP_SECW) + 2 * (SP_SHRINKS + 1);   // (sp_reserve grows it)
     rc = sp_alloc_layout(t, cap);
     if (rc == GBPE_OK) rc = sp_alloc_lexicon(t, cap, z / 16 + 1024);   // occurrences: the zone fronts shrinks move in
     if (rc != GBPE_OK) return rc;
@@ -178,43 +178,38 @@ int lex_root_build(gbpe_trainer* t, const S* store, const uint32_t* mul, uint64_
     // start zeroed, as WebGPU zero-initialises buffers)
     rc = sp_alloc_zone(t, z, 0);
     if (rc != GBPE_OK) return rc;
-    if (z) TR_HIP(t, hipMemcpyAsync(t->zbuf[0], zone, z * t->bps, hipMemcpyDeviceToDevice, s));
+    if (z) TR_HIP(t, hipMemcpyAsync(t->zbuf[0].p, zone, z * t->bps, hipMemcpyDeviceToDevice, s));
     // the zone passes' tile scratch
-    const uint64_t ntz = gbpe_div_up(t->zcap, TILE) + 1;
-    if (pool_malloc(t->ctx, &t->hitmask, ntz * TPB * sizeof(uint32_t)) != hipSuccess ||
-        pool_malloc(t->ctx, &t->tile_cnt, ntz * sizeof(uint32_t)) != hipSuccess ||
-        pool_malloc(t->ctx, &t->grpsum, (ntz / GRP + 2) * GSTR * sizeof(uint32_t)) != hipSuccess)
-        return gbpe_set_error(ctx, GBPE_E_OOM, "hipMalloc(zone scratch) failed");
-    TR_HIP(t, hipMemsetAsync(t->hitmask, 0, ntz * TPB * sizeof(uint32_t), s));
+    const uint64_t ntz = gbpe_div_up(t->zbuf[0].cap, TILE) + 1;
+    TR_HIP(t, t->hitmask.reserve(ctx, ntz * TPB));
+    TR_HIP(t, t->tile_cnt.reserve(ctx, ntz));
+    TR_HIP(t, t->grpsum.reserve(ctx, (ntz / GRP + 2) * GSTR));
+    TR_HIP(t, hipMemsetAsync(t->hitmask.p, 0, ntz * TPB * sizeof(uint32_t), s));
     // pair counts: the store weighted by its multiplicities, plus the zone
-    const uint64_t slots = (uint64_t)t->tb.mask + 1;
-    TR_HIP(t, hipMemsetAsync(t->tb.slots, 0, slots * sizeof(uint2), s));
-    TR_HIP(t, hipMemsetAsync(t->tb.bmax, 0, (uint64_t)t->tb.nblk * sizeof(uint64_t), s));
-    TR_HIP(t, hipMemsetAsync(t->tb.bmax2, 0, (uint64_t)t->tb.nblk * sizeof(uint64_t), s));
-    TR_HIP(t, hipMemsetAsync(t->tb.blive, 0, (uint64_t)t->tb.nblk * sizeof(uint32_t), s));
-    TR_HIP(t, hipMemsetAsync(&t->st->used, 0, sizeof(uint32_t), s));
+    rc = table_clear(t);
+    if (rc != GBPE_OK) return rc;
     if (t->lx_len > 1)
         hipLaunchKernelGGL(k_count_seg<S>, dim3(grid_persistent(ctx, gbpe_div_up(t->lx_len, TILE), 2)), dim3(TPB), 0, s,
-                           (const S*)t->lx_store, (const uint32_t*)t->lx_mul, t->lx_len, t->tb, t->st);
+                           (const S*)t->lx_store.p, (const uint32_t*)t->lx_mul.p, t->lx_len, t->tb, t->st.p);
     if (z > 1)
         hipLaunchKernelGGL(k_count_seg<S>, dim3(grid_persistent(ctx, gbpe_div_up(z, TILE), 2)), dim3(TPB), 0, s,
-                           (const S*)t->zbuf[0], (const uint32_t*)nullptr, z, t->tb, t->st);
-    hipLaunchKernelGGL(k_clear_dirty_all, dim3(gbpe_div_up(t->tb.nblk, 256)), dim3(256), 0, s, t->st, t->tb);
-    hipLaunchKernelGGL(k_refresh<S>, dim3(grid_blocks(ctx, t->tb.nblk, 4)), dim3(TPB), 0, s, t->st, 0u, 0, t->tb,
+                           (const S*)t->zbuf[0].p, (const uint32_t*)nullptr, z, t->tb, t->st.p);
+    hipLaunchKernelGGL(k_clear_dirty_all, dim3(gbpe_div_up(t->tb.nblk, 256)), dim3(256), 0, s, t->st.p, t->tb);
+    hipLaunchKernelGGL(k_refresh<S>, dim3(grid_blocks(ctx, t->tb.nblk, 4)), dim3(TPB), 0, s, t->st.p, 0u, 0, t->tb,
                        (S*)nullptr, (const uint32_t*)nullptr, (DevState*)nullptr);
-    hipLaunchKernelGGL(k_topcount, dim3(1), dim3(1024), 0, s, t->tb, t->d_u32);
+    hipLaunchKernelGGL(k_topcount, dim3(1), dim3(1024), 0, s, t->tb, t->d_u32.p);
     GBPE_LAUNCH_CHECK(ctx);
     rt.mark("zone+count");
     uint32_t hs[2] = {0, 0};
-    TR_HIP(t, hipMemcpyAsync(hs, t->d_u32, 8, hipMemcpyDeviceToHost, s));
+    TR_HIP(t, hipMemcpyAsync(hs, t->d_u32.p, 8, hipMemcpyDeviceToHost, s));
     TR_HIP(t, hipStreamSynchronize(s));
     if (hs[1]) return gbpe_set_error(ctx, GBPE_E_INVALID, "lexicon hand-over: the stores are not word/separator pairs");
     t->last_mc = hs[0];   // the zone-shrink target's count until a merge runs (as sp_enter)
     // states: body = every symbol before the zone (kept modulo 2^32 on the device)
     rc = sp_init_states(t, cap, (uint32_t)body_len, (uint32_t)z, (uint32_t)z);
     if (rc != GBPE_OK) return rc;
-    GBPE_LAUNCH_REFRESH(S, t->g_refresh, t->tb.nblk, s, t->st, 0u, 0, t->tb, (S*)nullptr, (const uint32_t*)nullptr,
-                        (DevState*)nullptr, (uint32_t*)nullptr, FusedSel(), t->part, (uint32_t*)nullptr);
+    GBPE_LAUNCH_REFRESH(S, t->g_refresh, t->tb.nblk, s, t->st.p, 0u, 0, t->tb, (S*)nullptr, (const uint32_t*)nullptr,
+                        (DevState*)nullptr, (uint32_t*)nullptr, FusedSel(), t->part.p, (uint32_t*)nullptr);
     GBPE_LAUNCH_CHECK(ctx);
     TR_HIP(t, hipStreamSynchronize(s));
     rt.mark("states");
@@ -250,19 +245,17 @@ extern "C" int gbpe_lexshard_create(gbpe_ctx* ctx, const uint8_t* bytes, uint64_
     gbpe_trainer* t = ls->t;
     hipStream_t s = ctx->stream;
     // the piece never merges: drop the other ping-pong buffer and the stream-pass scratch
-    pool_free(t->ctx, t->buf[t->cur ^ 1]);
-    t->buf[t->cur ^ 1] = nullptr;
-    pool_free(t->ctx, t->hitmask);
-    t->hitmask = nullptr;
+    t->buf[t->cur ^ 1].release();
+    t->hitmask.release();
     ls->u16 = t->u16;
     ls->bps = t->bps;
     ls->n = t->n;
-    if (!t->d_u32 && pool_malloc(t->ctx, &t->d_u32, 64) != hipSuccess) {
+    if (t->d_u32.reserve(ctx, 16) != hipSuccess) {
         gbpe_lexshard_destroy(ls);
         return gbpe_set_error(ctx, GBPE_E_OOM, "hipMalloc failed");
     }
-    hipLaunchKernelGGL(k_topcount, dim3(1), dim3(1024), 0, s, t->tb, t->d_u32);
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&ls->top, t->d_u32, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+    hipLaunchKernelGGL(k_topcount, dim3(1), dim3(1024), 0, s, t->tb, t->d_u32.p);
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&ls->top, t->d_u32.p, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess) {
         gbpe_lexshard_destroy(ls);
         return gbpe_set_error(ctx, GBPE_E_DEVICE, "lexshard: top count failed");
@@ -297,10 +290,10 @@ extern "C" int gbpe_lexshard_copy(gbpe_lexshard* ls, int what, void* dst, uint64
     const void* src = nullptr;
     uint64_t bytes = 0;
     switch (what) {
-        case GBPE_LEXSHARD_STORE: src = ls->store, bytes = ls->T * ls->bps; break;
-        case GBPE_LEXSHARD_MUL: src = ls->mul, bytes = ls->T * 4; break;
-        case GBPE_LEXSHARD_OCC: src = ls->occ, bytes = ls->nw * 4; break;
-        case GBPE_LEXSHARD_ZONE: src = ls->zone, bytes = ls->z * ls->bps; break;
+        case GBPE_LEXSHARD_STORE: src = ls->store.p, bytes = ls->T * ls->bps; break;
+        case GBPE_LEXSHARD_MUL: src = ls->mul.p, bytes = ls->T * 4; break;
+        case GBPE_LEXSHARD_OCC: src = ls->occ.p, bytes = ls->nw * 4; break;
+        case GBPE_LEXSHARD_ZONE: src = ls->zone.p, bytes = ls->z * ls->bps; break;
         default: return gbpe_set_error(ls->ctx, GBPE_E_INVALID, "lexshard_copy: unknown part %d", what);
     }
     if (bytes > cap_bytes) return gbpe_set_error(ls->ctx, GBPE_E_CAPACITY, "lexshard_copy: need %llu bytes",
@@ -325,20 +318,20 @@ extern "C" int gbpe_lexshard_remap(gbpe_lexshard* ls, const uint32_t* map, uint6
     if (!ls || (!map && n_map)) return GBPE_E_INVALID;
     if (!ls->built || ls->remapped) return gbpe_set_error(ls->ctx, GBPE_E_INVALID, "lexshard_remap: not built or done");
     hipStream_t s = ls->ctx->stream;
-    uint32_t* d = nullptr;
-    GBPE_HIP(ls->ctx, pool_malloc(ls->ctx, &d, (n_map + 1) * 4 + 8));
+    GbpeArray<uint32_t> own;
+    GBPE_HIP(ls->ctx, own.reserve(ls->ctx, n_map + 3));
+    uint32_t* d = own.p;
     hipError_t e = hipMemsetAsync(d, 0, 4, s);
     if (e == hipSuccess && n_map)
         e = hipMemcpyAsync(d + 1, map, n_map * 4, map_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
     if (e == hipSuccess && ls->nw) {
-        hipLaunchKernelGGL(k_lx_remap, dim3((uint32_t)gbpe_div_up(ls->nw, 256)), dim3(256), 0, s, ls->occ, ls->nw,
+        hipLaunchKernelGGL(k_lx_remap, dim3((uint32_t)gbpe_div_up(ls->nw, 256)), dim3(256), 0, s, ls->occ.p, ls->nw,
                            (const uint32_t*)(d + 1), n_map, d);
         e = hipGetLastError();
     }
     uint32_t bad = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&bad, d, 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    pool_free(ls->ctx, d);
     if (e != hipSuccess) return gbpe_set_error(ls->ctx, GBPE_E_DEVICE, "lexshard_remap: %s", hipGetErrorString(e));
     if (bad) return gbpe_set_error(ls->ctx, GBPE_E_INVALID, "lexshard_remap: a word id outside the map");
     ls->remapped = true;
@@ -349,10 +342,6 @@ extern "C" void gbpe_lexshard_destroy(gbpe_lexshard* ls) {
     if (!ls) return;
     if (ls->ctx && ls->ctx->stream) hipStreamSynchronize(ls->ctx->stream);
     if (ls->t) gbpe_trainer_destroy(ls->t);
-    pool_free(ls->ctx, ls->store);
-    pool_free(ls->ctx, ls->mul);
-    pool_free(ls->ctx, ls->occ);
-    pool_free(ls->ctx, ls->zone);
     delete ls;
 }
 
@@ -382,73 +371,67 @@ extern "C" int gbpe_trainer_create_from_lexicon(gbpe_ctx* ctx, const void* store
     t->n0 = t->n = body_len + zone_len;
     hipStream_t s = ctx->stream;
     RootTimer rt(s);
-    auto fail = [&](int code) {
-        gbpe_trainer_destroy(t);
-        return code;
-    };
-    // pair table (grown in place when crowded, as in the sector-sparse loop)
-    uint32_t lg = opts->table_log2 ? opts->table_log2 : 20;
-    if (lg < BLK_LOG2 + 1) lg = BLK_LOG2 + 1;
-    if (lg > 28) lg = 28;
-    int rc = table_resize(t, lg);
-    if (rc != GBPE_OK) return fail(rc);
-    if (pool_malloc(t->ctx, &t->st, sizeof(DevState)) != hipSuccess ||
-        pool_malloc(t->ctx, &t->d_log, (size_t)t->batch * 4 * sizeof(uint32_t)) != hipSuccess ||
-        pool_malloc(t->ctx, &t->d_u32, 64) != hipSuccess ||
-        pool_hmalloc(t->ctx, &t->h_st, sizeof(DevState)) != hipSuccess ||
-        pool_hmalloc(t->ctx, &t->h_log, (size_t)t->batch * 4 * sizeof(uint32_t)) != hipSuccess)
-        return fail(gbpe_set_error(ctx, GBPE_E_OOM, "hipMalloc(training state) failed"));
-    t->tb.used = &t->st->used;
-    TR_HIP(t, hipMemsetAsync(t->d_u32, 0, 64, s));
-    DevState init{};
-    init.n = (uint32_t)t->n;
-    init.next_id = t->next_id0;
-    memcpy(t->h_st, &init, sizeof(init));
-    TR_HIP(t, hipMemcpyAsync(t->st, t->h_st, sizeof(DevState), hipMemcpyHostToDevice, s));
-    // inputs (and the map) on the device
-    const uint64_t bps = t->bps;
-    const void* d_store = store;
-    const uint32_t* d_mul = mul;
-    const void* d_zone = zone;
-    void* tmp = nullptr;
-    if (!input_on_device) {
-        if (pool_malloc(t->ctx, &tmp, store_len * (bps + 4) + zone_len * bps + 64) != hipSuccess)
-            return fail(gbpe_set_error(ctx, GBPE_E_OOM, "hipMalloc(hand-over input) failed"));
-        char* p = (char*)tmp;
-        if ((store_len && (hipMemcpyAsync(p, store, store_len * bps, hipMemcpyHostToDevice, s) != hipSuccess ||
-                           hipMemcpyAsync(p + store_len * bps, mul, store_len * 4, hipMemcpyHostToDevice, s) != hipSuccess)) ||
-            hipMemcpyAsync(p + store_len * (bps + 4), zone, zone_len * bps, hipMemcpyHostToDevice, s) != hipSuccess) {
-            pool_free(t->ctx, tmp);
-            return fail(gbpe_set_error(ctx, GBPE_E_DEVICE, "hand-over upload failed"));
-        }
-        d_store = p;
-        d_mul = (const uint32_t*)(p + store_len * bps);
-        d_zone = p + store_len * (bps + 4);
-    }
-    rt.mark("upload");
-    uint32_t* d_map = nullptr;
-    if (pool_malloc(t->ctx, &d_map, (store_len / 2 + 2) * 4) != hipSuccess) {
-        pool_free(t->ctx, tmp);
-        return fail(gbpe_set_error(ctx, GBPE_E_OOM, "hipMalloc(map) failed"));
-    }
     uint64_t nm = 0;
-    rc = t->u16 ? lex_root_build<uint16_t>(t, (const uint16_t*)d_store, d_mul, store_len, (const uint16_t*)d_zone,
-                                           zone_len, body_len, d_map, &nm, rt)
-                : lex_root_build<uint32_t>(t, (const uint32_t*)d_store, d_mul, store_len, (const uint32_t*)d_zone,
-                                           zone_len, body_len, d_map, &nm, rt);
-    if (rc == GBPE_OK && map_out) {
-        if (map_cap < nm) rc = gbpe_set_error(ctx, GBPE_E_CAPACITY, "lexicon hand-over: map needs %llu entries",
-                                              (unsigned long long)nm);
-        else if (nm && (hipMemcpyAsync(map_out, d_map, nm * 4, map_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                                       s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess))
-            rc = gbpe_set_error(ctx, GBPE_E_DEVICE, "lexicon hand-over: map copy failed");
-    }
-    hipStreamSynchronize(s);
-    rt.mark("map");
-    pool_free(t->ctx, d_map);
-    pool_free(t->ctx, tmp);
+    // (every error return, TR_HIP's included, destroys the trainer below)
+    auto build = [&]() -> int {
+        if (t->st.reserve(ctx, 1) != hipSuccess || t->d_log.reserve(ctx, (size_t)t->batch * 4) != hipSuccess ||
+            t->d_u32.reserve(ctx, 16) != hipSuccess || t->h_st.reserve(ctx, 1) != hipSuccess ||
+            t->h_log.reserve(ctx, (size_t)t->batch * 4) != hipSuccess)
+            return gbpe_set_error(ctx, GBPE_E_OOM, "hipMalloc(training state) failed");
+        // pair table (grown in place when crowded, as in the sector-sparse loop)
+        uint32_t lg = opts->table_log2 ? opts->table_log2 : 20;
+        if (lg < BLK_LOG2 + 1) lg = BLK_LOG2 + 1;
+        if (lg > 28) lg = 28;
+        int rc = table_resize(t, lg);
+        if (rc != GBPE_OK) return rc;
+        TR_HIP(t, hipMemsetAsync(t->d_u32.p, 0, 64, s));
+        DevState init{};
+        init.n = (uint32_t)t->n;
+        init.next_id = t->next_id0;
+        memcpy(t->h_st.p, &init, sizeof(init));
+        TR_HIP(t, hipMemcpyAsync(t->st.p, t->h_st.p, sizeof(DevState), hipMemcpyHostToDevice, s));
+        // inputs (and the map) on the device
+        const uint64_t bps = t->bps;
+        const void* d_store = store;
+        const uint32_t* d_mul = mul;
+        const void* d_zone = zone;
+        GbpeArray<char> tmp;
+        if (!input_on_device) {
+            if (tmp.reserve(ctx, store_len * (bps + 4) + zone_len * bps + 64) != hipSuccess)
+                return gbpe_set_error(ctx, GBPE_E_OOM, "hipMalloc(hand-over input) failed");
+            char* p = tmp.p;
+            if ((store_len && (hipMemcpyAsync(p, store, store_len * bps, hipMemcpyHostToDevice, s) != hipSuccess ||
+                               hipMemcpyAsync(p + store_len * bps, mul, store_len * 4, hipMemcpyHostToDevice, s) != hipSuccess)) ||
+                hipMemcpyAsync(p + store_len * (bps + 4), zone, zone_len * bps, hipMemcpyHostToDevice, s) != hipSuccess)
+                return gbpe_set_error(ctx, GBPE_E_DEVICE, "hand-over upload failed");
+            d_store = p;
+            d_mul = (const uint32_t*)(p + store_len * bps);
+            d_zone = p + store_len * (bps + 4);
+        }
+        rt.mark("upload");
+        GbpeArray<uint32_t> d_map;
+        if (d_map.reserve(ctx, store_len / 2 + 2) != hipSuccess) return gbpe_set_error(ctx, GBPE_E_OOM, "hipMalloc(map) failed");
+        rc = t->u16 ? lex_root_build<uint16_t>(t, (const uint16_t*)d_store, d_mul, store_len, (const uint16_t*)d_zone,
+                                               zone_len, body_len, d_map.p, &nm, rt)
+                    : lex_root_build<uint32_t>(t, (const uint32_t*)d_store, d_mul, store_len, (const uint32_t*)d_zone,
+                                               zone_len, body_len, d_map.p, &nm, rt);
+        if (rc == GBPE_OK && map_out) {
+            if (map_cap < nm) rc = gbpe_set_error(ctx, GBPE_E_CAPACITY, "lexicon hand-over: map needs %llu entries",
+                                                  (unsigned long long)nm);
+            else if (nm && (hipMemcpyAsync(map_out, d_map.p, nm * 4, map_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                                           s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess))
+                rc = gbpe_set_error(ctx, GBPE_E_DEVICE, "lexicon hand-over: map copy failed");
+        }
+        hipStreamSynchronize(s);
+        rt.mark("map");
+        return rc;
+    };
+    const int rc = build();
     *n_map = nm;
-    if (rc != GBPE_OK) return fail(rc);
+    if (rc != GBPE_OK) {
+        gbpe_trainer_destroy(t);
+        return rc;
+    }
     *out = t;
     return GBPE_OK;
 }
@@ -458,30 +441,23 @@ template <typename S>
 int trainer_expand(gbpe_trainer* t, const uint32_t* d_prefix, uint64_t n_prefix, uint32_t* d_out, uint64_t* total) {
     hipStream_t s = t->ctx->stream;
     const uint64_t nown = t->lx_nocc, no = n_prefix + nown;
-    uint32_t* occ = nullptr;
-    S* tmp = nullptr;
-    auto release = gbpe_scope_exit([&] {   // every return path, TR_HIP's included
-        pool_free(t->ctx, tmp);
-        pool_free(t->ctx, occ);
-    });
+    GbpeArray<uint32_t> occ;
+    GbpeArray<S> tmp;
     const uint64_t z = (uint32_t)t->n - t->h_st->B;
-    TR_HIP(t, pool_malloc(t->ctx, &occ, (no + 1) * 4));
-    if (n_prefix) TR_HIP(t, hipMemcpyAsync(occ, d_prefix, n_prefix * 4, hipMemcpyDeviceToDevice, s));
-    if (nown) TR_HIP(t, hipMemcpyAsync(occ + n_prefix, t->lx_occ, nown * 4, hipMemcpyDeviceToDevice, s));
+    TR_HIP(t, occ.reserve(t->ctx, no + 1));
+    if (n_prefix) TR_HIP(t, hipMemcpyAsync(occ.p, d_prefix, n_prefix * 4, hipMemcpyDeviceToDevice, s));
+    if (nown) TR_HIP(t, hipMemcpyAsync(occ.p + n_prefix, t->lx_occ.p, nown * 4, hipMemcpyDeviceToDevice, s));
     // the body's total, then the zone after it
     uint64_t tot = 0;
-    if (pool_malloc(t->ctx, &tmp, (t->n + 64) * sizeof(S)) != hipSuccess) {
-        tmp = nullptr;
-        return gbpe_set_error(t->ctx, GBPE_E_OOM, "expand: hipMalloc(%llu symbols) failed", (unsigned long long)t->n);
-    }
-    int rc = lx_expand<S>(t, tmp, t->n - z, &tot, occ, no);   // (checks the total before writing)
+    TR_HIP(t, tmp.reserve(t->ctx, t->n + 64));
+    int rc = lx_expand<S>(t, tmp.p, t->n - z, &tot, occ.p, no);   // (checks the total before writing)
     TR_HIP(t, hipStreamSynchronize(s));
     if (rc == GBPE_OK && tot + z != t->n)
         rc = gbpe_set_error(t->ctx, GBPE_E_INVALID, "expand: the occurrence lists hold %llu body symbols, the trainer %llu",
                             (unsigned long long)tot, (unsigned long long)(t->n - z));
     if (rc == GBPE_OK) {
-        TR_HIP(t, hipMemcpyAsync(tmp + tot, t->zbuf[t->zcur], z * sizeof(S), hipMemcpyDeviceToDevice, s));
-        hipLaunchKernelGGL(k_export_symbols<S>, dim3((uint32_t)gbpe_div_up(t->n, 256)), dim3(256), 0, s, (const S*)tmp,
+        TR_HIP(t, hipMemcpyAsync(tmp.p + tot, t->zbuf[t->zcur].p, z * sizeof(S), hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(k_export_symbols<S>, dim3((uint32_t)gbpe_div_up(t->n, 256)), dim3(256), 0, s, (const S*)tmp.p,
                            d_out, t->n);
         GBPE_LAUNCH_CHECK(t->ctx);
         TR_HIP(t, hipStreamSynchronize(s));
@@ -499,29 +475,22 @@ extern "C" int gbpe_trainer_expand(gbpe_trainer* t, const uint32_t* prefix_occ, 
     if (!t->sp || !t->lex) return gbpe_set_error(t->ctx, GBPE_E_INVALID, "expand: the trainer holds no word lexicon");
     if (cap < t->n) return gbpe_set_error(t->ctx, GBPE_E_CAPACITY, "expand: need %llu", (unsigned long long)t->n);
     hipStream_t s = t->ctx->stream;
-    TR_HIP(t, hipMemcpyAsync(t->h_st, t->st, sizeof(DevState), hipMemcpyDeviceToHost, s));
+    TR_HIP(t, hipMemcpyAsync(t->h_st.p, t->st.p, sizeof(DevState), hipMemcpyDeviceToHost, s));
     TR_HIP(t, hipStreamSynchronize(s));
-    uint32_t* d_pre = nullptr;
-    uint32_t* d_out = out_on_device ? out : nullptr;
-    uint32_t* d_own = nullptr;   // the staging output this call allocated
-    auto release = gbpe_scope_exit([&] {   // every return path, TR_HIP's included
-        pool_free(t->ctx, d_pre);
-        pool_free(t->ctx, d_own);
-    });
+    GbpeArray<uint32_t> d_pre, d_own;   // the staged prefix and output this call allocated
+    uint32_t* d_out = out;
     if (n_prefix && !prefix_on_device) {
-        TR_HIP(t, pool_malloc(t->ctx, &d_pre, n_prefix * 4));
-        TR_HIP(t, hipMemcpyAsync(d_pre, prefix_occ, n_prefix * 4, hipMemcpyHostToDevice, s));
+        TR_HIP(t, d_pre.reserve(t->ctx, n_prefix));
+        TR_HIP(t, hipMemcpyAsync(d_pre.p, prefix_occ, n_prefix * 4, hipMemcpyHostToDevice, s));
+        prefix_occ = d_pre.p;
     }
-    if (!d_out) {
-        if (pool_malloc(t->ctx, &d_own, t->n * 4 + 4) != hipSuccess) {
-            d_own = nullptr;
-            return gbpe_set_error(t->ctx, GBPE_E_OOM, "expand: hipMalloc(output) failed");
-        }
-        d_out = d_own;
+    if (!out_on_device) {
+        TR_HIP(t, d_own.reserve(t->ctx, t->n + 1));
+        d_out = d_own.p;
     }
     uint64_t tot = 0;
-    int rc = t->u16 ? trainer_expand<uint16_t>(t, d_pre ? d_pre : prefix_occ, n_prefix, d_out, &tot)
-                    : trainer_expand<uint32_t>(t, d_pre ? d_pre : prefix_occ, n_prefix, d_out, &tot);
+    int rc = t->u16 ? trainer_expand<uint16_t>(t, prefix_occ, n_prefix, d_out, &tot)
+                    : trainer_expand<uint32_t>(t, prefix_occ, n_prefix, d_out, &tot);
     if (rc == GBPE_OK && !out_on_device &&
         (hipMemcpy(out, d_out, t->n * 4, hipMemcpyDeviceToHost) != hipSuccess))
         rc = gbpe_set_error(t->ctx, GBPE_E_DEVICE, "expand: copy to host failed");

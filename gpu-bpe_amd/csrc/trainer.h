@@ -20,70 +20,60 @@ struct gbpe_trainer {
     uint64_t n0 = 0, cap_syms = 0;
     uint64_t n_prev0 = 0;        // created from a state: its previous-stream length (export before any merge)
     uint32_t next_id0 = 256;     // Vocab.nextTokenId at creation
-    void* buf[2] = {nullptr, nullptr};
+    GbpeArray<void> buf[2];      // cap_syms symbols each
     int cur = 0;                 // index of the buffer holding the stream
     uint64_t n = 0;              // host copy of the stream length (the device state holds it modulo 2^32:
                                  // a lexicon trainer built from shards may exceed 32 bits)
     uint32_t needed = 0, done = 0;
     bool stop = false;
     uint32_t flags = 0, batch = GBPE_BATCH_SIZE;
-    DevState* st = nullptr;
-    DevState* h_st = nullptr;    // pinned
-    uint32_t* d_log = nullptr;
-    uint32_t* h_log = nullptr;   // pinned
-    Table tb{};
+    GbpeArray<DevState> st;
+    GbpeArray<DevState, true> h_st;
+    GbpeArray<uint32_t> d_log;
+    GbpeArray<uint32_t, true> h_log;
+    Table tb{};                  // the kernels' view of the six arrays below (table_resize)
+    GbpeArray<uint2> tb_slots;
+    GbpeArray<uint64_t> tb_bmax, tb_bmax2;
+    GbpeArray<uint32_t> tb_dirty, tb_dlist, tb_blive;
     uint32_t table_log2 = 22;
-    uint32_t* hitmask = nullptr;
-    uint32_t* tile_cnt = nullptr;
-    uint32_t* grpsum = nullptr;
+    GbpeArray<uint32_t> hitmask, tile_cnt, grpsum;
     // stats
     uint64_t bytes_moved = 0;
-    uint64_t max_live = 0;
     double ms_merge = 0, ms_select = 0, ms_other = 0, ms_delta = 0, ms_compact = 0;
     uint64_t timed_merges = 0;
     std::vector<hipEvent_t> evs;
     // sector-sparse loop
     bool sp = false;             // the stream is in the sector layout
-    uint32_t sp_secw = 256;      // sector window (symbols)
     uint32_t max_id = 0;         // exclusive bound of every token id of the run (bitmap rows)
     uint32_t last_mc = 0;        // count of the last merge run
     int bcur = 0;                // dense buffer holding the body sectors
     uint32_t nsec = 0;
-    uint64_t nsec_cap = 0, loc_cap = 0;
     uint32_t bend = 0;           // end of the body's sector windows in the body buffer
     uint32_t sp_shrinks = 0;     // zone shrinks since the last entry
-    uint2* sec = nullptr;        // {start, count} per sector
-    uint32_t* sp_loc = nullptr;  // per-sector scratch (starts / scan)
-    uint64_t* sp_blk = nullptr;  // scan block totals
-    uint32_t* bits = nullptr;    // presence bitmap, rows = token ids, W words per row
-    uint32_t* sig = nullptr;     // per-sector pair signatures (SP_SIGW words each)
-    uint64_t sig_cap = 0;
+    GbpeArray<uint2> sec;        // {start, count} per sector
+    GbpeArray<uint32_t> sp_loc;  // per-sector scratch (starts / scan)
+    GbpeArray<uint64_t> sp_blk;  // scan block totals
+    GbpeArray<uint32_t> bits;    // presence bitmap, rows = token ids, W words per row
+    GbpeArray<uint32_t> sig;     // per-sector pair signatures (SP_SIGW words each)
     uint64_t sp_age = 0;         // sparse merges since the signatures were built
     uint64_t sp_bits_age = 0;    // ... since the token bitmap was built
-    uint64_t bits_cap = 0;       // words
     uint32_t W = 0;
-    void* zbuf[2] = {nullptr, nullptr};
-    void* wtmp = nullptr;        // stale-window source copy
-    uint64_t zcap = 0;           // zone buffer capacity (symbols)
+    GbpeArray<void> zbuf[2];     // zone buffers (capacity in symbols, the same for all three)
+    GbpeArray<void> wtmp;        // stale-window source copy
     int zcur = 0;                // zone buffer holding the zone
-    DevState* zst = nullptr;     // the zone's loop state
-    DevState* h_zst = nullptr;   // pinned
-    uint32_t* d_u32 = nullptr;   // small device scratch
-    uint64_t* part = nullptr;    // k_refresh workgroup maxima (sparse selection)
+    GbpeArray<DevState> zst;     // the zone's loop state
+    GbpeArray<DevState, true> h_zst;
+    GbpeArray<uint32_t> d_u32;   // small device scratch
+    GbpeArray<uint64_t> part;    // k_refresh workgroup maxima (sparse selection)
     uint32_t grow_used_pct = 50;   // the table is rebuilt once its occupied slots (dead included) pass this %
     uint32_t grow_live_pct = 25;   // ... into the smallest 2^k slots its live pairs fill to at most this %
-    uint2* zdr_out = nullptr;    // the multi-tile zone passes' delta dumps (ZdrView, train_dev.h)
-    uint32_t* zdr_offs = nullptr;
-    uint32_t* zdr_flag = nullptr;
+    GbpeArray<uint2> zdr_out;    // the multi-tile zone passes' delta dumps (ZdrView, train_dev.h)
+    GbpeArray<uint32_t> zdr_offs, zdr_flag;
     uint32_t zdr_ntile = 0;      // tile-workgroup dumps the buffers hold (+ ZDR_P churn workgroups)
-    bool zdr_on = true;          // two-stage zone delta reduction (false: every workgroup flushes, the round-2 path)
-    uint32_t* zseg = nullptr;    // ZSegState: the zone segments' per-merge hand-off (k_refresh zeroes it)
-    uint32_t zseg_mode = 1;      // 1 = zone segments for zones beyond zone_one (up to 1M), 0 = off
+    GbpeArray<uint32_t> zseg;    // ZSegState: the zone segments' per-merge hand-off (k_refresh zeroes it)
     uint32_t table_grows = 0;    // crowded-table rebuilds (same size or larger)
-    uint64_t* wg_bytes = nullptr;   // bytes moved per k_body workgroup (each its own counter)
-    uint32_t delta_mt = 2048;       // dense k_delta: multi-tile workgroups from this many tiles (0 = never; GBPE_DEBUG delta_mt)
-    uint32_t delta_tpw = 8;         // ... of 8, 16 or 32 tiles
-    uint64_t wg_cap = 0;
+    GbpeArray<uint64_t> wg_bytes;   // bytes moved per k_body workgroup (each its own counter)
+    uint32_t delta_mt = 2048;       // dense k_delta: workgroups of 8 tiles from this many tiles (0 = never; GBPE_DEBUG delta_mt)
     double ms_sparse = 0, ms_dense = 0;   // GBPE_TRAIN_TIMING: merge passes (without selection / refresh) by mode
     double ms_body = 0;          // GBPE_TRAIN_TIMING: k_body alone
     double ms_create = 0;        // host wall time of trainer creation
@@ -91,11 +81,8 @@ struct gbpe_trainer {
     uint32_t g_refresh = 0;
     uint64_t sp_merges = 0, sp_sectors = 0, sp_zone = 0;
     uint32_t sp_enters = 0, sp_exits = 0;
-    uint32_t sp_div = 64;        // enter when last_mc * sp_div <= n
     uint32_t sp_cooldown = 0;    // steps to stay dense after an abort
-    uint32_t* d_bhist = nullptr; // byte-pair histogram of the first count (65,536 u32)
-    uint32_t count_bytes_on = 1; // first count by the byte-pair histogram (0: hashed k_count_full)
-    uint32_t lx_size_on = 1;     // word table sized from a sampled distinct count (0: from the word count)
+    GbpeArray<uint32_t> d_bhist; // byte-pair histogram of the first count (65,536 u32)
     uint32_t seg8 = 1;           // zone segments of 8K symbols for zones <= 512K (GBPE_DEBUG seg8; 0: 16K)
     uint32_t zseg_lo = 8192;     // zones above this many symbols run as zone segments (GBPE_DEBUG zslo; 16384
                                  // = round 4: 1 GiB 0.557 vs 0.548 s, C2 equal, C1 11.6 vs 11.8 ms, profiles/r5/s30)
@@ -110,11 +97,8 @@ struct gbpe_trainer {
     uint32_t lx_div = 16;        // with the lexicon: enter once next_mc * lx_div <= n, from the first step on (GBPE_DEBUG lxdiv)
     uint32_t sub_zone = 1u << 20;   // sparse steps run in sub-steps of sub_k merges while the zone exceeds this
     uint32_t sub_k = 16;            // (the zone shrinks between them; GBPE_DEBUG subz, subk)
-    bool zone16 = true;             // u16 zones of 8K-16K symbols: the 16-per-thread zone pass 
-    uint32_t sp_zt = 5;          // zone target = sp_zt * last_mc + 64 (>= zone_f; GBPE_DEBUG zt; 4/5/6/7 measured
-                                 // 0.895/0.893/0.918/0.918 s at 1 GiB with zone_f 3)
-    uint32_t shrink_pct = 200;   // shrink once the zone exceeds shrink_pct % of the target + 4096 
-    uint32_t zone_f = 3;         // single-GPU zone rule factor (sel_inline, >= 3)
+    uint32_t sp_zt = 5;          // zone target = sp_zt * last_mc + 64 (>= SP_ZONE_F; GBPE_DEBUG zt; 4/5/6/7 measured
+                                 // 0.895/0.893/0.918/0.918 s at 1 GiB with SP_ZONE_F 3)
     uint32_t refresh_blocks = 0; // k_refresh grid (0 = 2 per CU)
     uint32_t refresh_late_z = 16384; // ... for zones of at most this many symbols
     uint32_t refresh_late = 64;  // k_refresh grid of late steps (0 = unchanged)
@@ -127,8 +111,8 @@ struct gbpe_trainer {
     uint64_t pair_done = 0;      // merges run as the second of a launch (stats)
     uint32_t pair_prej = 0;      // GBPE_DEBUG prej=k (tests): the verdict rejects every k-th candidate (0: off)
     uint32_t ptrace = 0;         // GBPE_DEBUG ptrace=1: every step's form and pairing on stderr
-    uint32_t* d_clog = nullptr;  // GBPE_SPARSE_TRACE: per-merge candidate / hit sectors
-    uint32_t* h_clog = nullptr;
+    GbpeArray<uint32_t> d_clog;  // GBPE_SPARSE_TRACE: per-merge candidate / hit sectors
+    GbpeArray<uint32_t, true> h_clog;
     FILE* trace = nullptr;
     uint32_t htime = 0;          // GBPE_DEBUG htime=1: host enqueue / wait split of every step (stderr at destroy)
     double ht_enq = 0, ht_wait = 0, ht_enq_late = 0, ht_wait_late = 0, ht_pre = 0, ht_post = 0, ht_out = 0;
@@ -142,15 +126,14 @@ struct gbpe_trainer {
     bool lex_on = true;          // GBPE_DEBUG lexicon=0: never
     bool lex_only = false;       // built from shard lexicons (gbpe_trainer_create_from_lexicon): no dense stream,
                                  // the body's stream order lives on the ranks; never leaves the sparse loop
-    void* lx_store = nullptr;    // distinct words, each followed by a 0 separator (S symbols)
-    uint32_t* lx_mul = nullptr;  // per store symbol: its word's occurrences (0 = separator / padding)
-    uint64_t lx_cap = 0, lx_len = 0;   // store symbols: capacity, used
-    uint32_t* lx_occ = nullptr;  // body words in stream order: uid, or LX_LIT | symbol
-    uint64_t lx_occ_cap = 0, lx_nocc = 0;
-    uint32_t* lx_w0 = nullptr;   // first uid of each sector window
-    uint32_t lx_nuid = 0, lx_uid_cap = 0;
-    void* lx_tmp = nullptr;      // build / expansion scratch (grown, kept)
-    uint64_t lx_tmp_bytes = 0;
+    GbpeArray<void> lx_store;    // distinct words, each followed by a 0 separator (S symbols)
+    GbpeArray<uint32_t> lx_mul;  // per store symbol: its word's occurrences (0 = separator / padding)
+    uint64_t lx_len = 0;         // store symbols used
+    GbpeArray<uint32_t> lx_occ;  // body words in stream order: uid, or LX_LIT | symbol
+    uint64_t lx_nocc = 0;
+    GbpeArray<uint32_t> lx_w0;   // first uid of each sector window
+    uint32_t lx_nuid = 0;
+    GbpeArray<void> lx_tmp;      // build / expansion scratch in bytes (grown, kept)
     uint64_t lx_words = 0, lx_builds = 0, lx_fallbacks = 0;   // stats
 };
 
@@ -161,14 +144,8 @@ int tr_err(gbpe_trainer* t, int code, const char* msg) { return gbpe_set_error(t
 #define TR_HIP(t, call) GBPE_HIP((t)->ctx, call)
 
 // the symbols the sparse kernels merge: the lexicon store, or the body sectors in place
-inline void* sp_body(const gbpe_trainer* t) { return t->lex ? t->lx_store : t->buf[t->bcur]; }
-inline uint32_t* sp_mul(const gbpe_trainer* t) { return t->lex ? t->lx_mul : nullptr; }
-// the single-GPU selection's zone rule (sel_inline)
-inline SelShard sel_single(const gbpe_trainer* t) {
-    SelShard sh;
-    sh.zf = t->zone_f;
-    return sh;
-}
+inline void* sp_body(const gbpe_trainer* t) { return t->lex ? t->lx_store.p : t->buf[t->bcur].p; }
+inline uint32_t* sp_mul(const gbpe_trainer* t) { return t->lex ? t->lx_mul.p : nullptr; }
 
 
 uint32_t grid_persistent(const gbpe_ctx* ctx, uint64_t work_tiles, uint32_t per_cu) {
@@ -181,86 +158,82 @@ uint32_t grid_blocks(const gbpe_ctx* ctx, uint32_t nblk, uint32_t per_cu) {
     return std::max<uint32_t>(grid_persistent(ctx, nblk, per_cu), (uint32_t)gbpe_div_up(nblk, 64));
 }
 
-// the partial maxima of the sparse selection (one per k_refresh workgroup), sized
+// the partial maxima of the sparse selection: two keys per k_refresh workgroup, sized
 // for the table's blocks (sparse entry; after every table resize)
-int part_alloc(gbpe_trainer* t) {
-    pool_free(t->ctx, t->part);
-    t->part = nullptr;
-    TR_HIP(t, pool_malloc(t->ctx, &t->part, 2ull * (t->tb.nblk + 1) * sizeof(uint64_t)));   // two keys per workgroup
+int part_reserve(gbpe_trainer* t) {
+    TR_HIP(t, t->part.reserve(t->ctx, 2ull * (t->tb.nblk + 1)));
     return GBPE_OK;
 }
 
-// new (empty) table arrays of 2^lg slots; the caller recounts (table_rebuild)
+// (empty) table arrays of 2^lg slots; the caller recounts (table_rebuild)
 int table_resize(gbpe_trainer* t, uint32_t lg) {
     hipStream_t s = t->ctx->stream;
     TR_HIP(t, hipStreamSynchronize(s));
-    pool_free(t->ctx, t->tb.slots);
-    pool_free(t->ctx, t->tb.bmax);
-    pool_free(t->ctx, t->tb.bmax2);
-    pool_free(t->ctx, t->tb.dirty);
-    pool_free(t->ctx, t->tb.dlist);
-    pool_free(t->ctx, t->tb.blive);
-    t->tb.slots = nullptr, t->tb.bmax = nullptr, t->tb.bmax2 = nullptr, t->tb.dirty = nullptr, t->tb.dlist = nullptr, t->tb.blive = nullptr;
     const uint64_t slots = 1ull << lg;
+    const uint32_t nblk = (uint32_t)(slots >> BLK_LOG2);
+    TR_HIP(t, t->tb_slots.reserve(t->ctx, slots));
+    TR_HIP(t, t->tb_bmax.reserve(t->ctx, nblk));
+    TR_HIP(t, t->tb_bmax2.reserve(t->ctx, nblk));
+    TR_HIP(t, t->tb_dirty.reserve(t->ctx, nblk));
+    TR_HIP(t, t->tb_dlist.reserve(t->ctx, nblk + 1));
+    TR_HIP(t, t->tb_blive.reserve(t->ctx, nblk));
     t->table_log2 = lg;
-    t->tb.mask = (uint32_t)(slots - 1);
-    t->tb.nblk = (uint32_t)(slots >> BLK_LOG2);
-    if (pool_malloc(t->ctx, &t->tb.slots, slots * sizeof(uint2)) != hipSuccess ||
-        pool_malloc(t->ctx, &t->tb.bmax, t->tb.nblk * sizeof(uint64_t)) != hipSuccess ||
-        pool_malloc(t->ctx, &t->tb.bmax2, t->tb.nblk * sizeof(uint64_t)) != hipSuccess ||
-        pool_malloc(t->ctx, &t->tb.dirty, t->tb.nblk * sizeof(uint32_t)) != hipSuccess ||
-        pool_malloc(t->ctx, &t->tb.dlist, (t->tb.nblk + 1) * sizeof(uint32_t)) != hipSuccess ||
-        pool_malloc(t->ctx, &t->tb.blive, t->tb.nblk * sizeof(uint32_t)) != hipSuccess)
-        return gbpe_set_error(t->ctx, GBPE_E_OOM, "hipMalloc(pair table, 2^%u slots) failed", lg);
-    TR_HIP(t, hipMemsetAsync(t->tb.dirty, 0, t->tb.nblk * sizeof(uint32_t), s));
-    t->g_refresh = grid_blocks(t->ctx, t->tb.nblk, 2);
-    if (t->refresh_blocks) t->g_refresh = std::max<uint32_t>(t->refresh_blocks, (uint32_t)gbpe_div_up(t->tb.nblk, 64));
-    if (t->part) return part_alloc(t);   // one partial maximum per k_refresh workgroup
+    t->tb = Table{t->tb_slots.p, (uint32_t)(slots - 1), t->tb_bmax.p, t->tb_bmax2.p, t->tb_dirty.p,
+                  t->tb_dlist.p, t->tb_blive.p, nblk, &t->st->used};
+    TR_HIP(t, hipMemsetAsync(t->tb.dirty, 0, nblk * sizeof(uint32_t), s));
+    t->g_refresh = grid_blocks(t->ctx, nblk, 2);
+    if (t->refresh_blocks) t->g_refresh = std::max<uint32_t>(t->refresh_blocks, (uint32_t)gbpe_div_up(nblk, 64));
+    if (t->part.p) return part_reserve(t);
+    return GBPE_OK;
+}
+
+// an empty table: slots, block maxima, live counts and the occupied-slot counter
+// (the dirty flags are the caller's: k_clear_dirty_all after its recount)
+int table_clear(gbpe_trainer* t) {
+    hipStream_t s = t->ctx->stream;
+    TR_HIP(t, hipMemsetAsync(t->tb.slots, 0, ((uint64_t)t->tb.mask + 1) * sizeof(uint2), s));
+    TR_HIP(t, hipMemsetAsync(t->tb.bmax, 0, (uint64_t)t->tb.nblk * sizeof(uint64_t), s));
+    TR_HIP(t, hipMemsetAsync(t->tb.bmax2, 0, (uint64_t)t->tb.nblk * sizeof(uint64_t), s));
+    TR_HIP(t, hipMemsetAsync(t->tb.blive, 0, (uint64_t)t->tb.nblk * sizeof(uint32_t), s));
+    TR_HIP(t, hipMemsetAsync(&t->st->used, 0, sizeof(uint32_t), s));
     return GBPE_OK;
 }
 
 // bytes_only: every symbol is a byte (the stream as trainer creation builds it)
 int table_rebuild(gbpe_trainer* t, bool bytes_only = false) {
     hipStream_t s = t->ctx->stream;
-    const uint64_t slots = (uint64_t)t->tb.mask + 1;
-    TR_HIP(t, hipMemsetAsync(t->tb.slots, 0, slots * sizeof(uint2), s));
-    TR_HIP(t, hipMemsetAsync(t->tb.bmax, 0, (uint64_t)t->tb.nblk * sizeof(uint64_t), s));
-    TR_HIP(t, hipMemsetAsync(t->tb.bmax2, 0, (uint64_t)t->tb.nblk * sizeof(uint64_t), s));
-    TR_HIP(t, hipMemsetAsync(t->tb.blive, 0, (uint64_t)t->tb.nblk * sizeof(uint32_t), s));
-    TR_HIP(t, hipMemsetAsync(&t->st->used, 0, sizeof(uint32_t), s));
+    int rc = table_clear(t);
+    if (rc != GBPE_OK) return rc;
     const uint64_t ntiles = gbpe_div_up(t->n, TILE);
     const uint32_t g = grid_persistent(t->ctx, ntiles, 2);
-    if (bytes_only && t->count_bytes_on) {
-        if (!t->d_bhist && pool_malloc(t->ctx, (void**)&t->d_bhist, 65536 * sizeof(uint32_t)) != hipSuccess) {
-            t->d_bhist = nullptr;
-            return gbpe_set_error(t->ctx, GBPE_E_OOM, "hipMalloc(byte-pair histogram) failed");
-        }
-        uint32_t* gh = t->d_bhist;
+    if (bytes_only) {   // the first count: by the byte-pair histogram
+        TR_HIP(t, t->d_bhist.reserve(t->ctx, 65536));
+        uint32_t* gh = t->d_bhist.p;
         TR_HIP(t, hipMemsetAsync(gh, 0, 65536 * sizeof(uint32_t), s));
         const uint64_t ncu = t->ctx->num_cu > 0 ? (uint64_t)t->ctx->num_cu : 256u;
         const uint32_t gb = 2u * (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(ncu, gbpe_div_up(t->n, 16ull * CB_T)));
         if (t->u16)
-            hipLaunchKernelGGL(k_count_bytes<uint16_t>, dim3(gb), dim3(CB_T), 0, s, (const uint16_t*)t->buf[t->cur],
+            hipLaunchKernelGGL(k_count_bytes<uint16_t>, dim3(gb), dim3(CB_T), 0, s, (const uint16_t*)t->buf[t->cur].p,
                                (uint64_t)t->n, gh);
         else
-            hipLaunchKernelGGL(k_count_bytes<uint32_t>, dim3(gb), dim3(CB_T), 0, s, (const uint32_t*)t->buf[t->cur],
+            hipLaunchKernelGGL(k_count_bytes<uint32_t>, dim3(gb), dim3(CB_T), 0, s, (const uint32_t*)t->buf[t->cur].p,
                                (uint64_t)t->n, gh);
-        hipLaunchKernelGGL(k_count_hist, dim3(256), dim3(256), 0, s, (const uint32_t*)gh, t->st, t->tb);
+        hipLaunchKernelGGL(k_count_hist, dim3(256), dim3(256), 0, s, (const uint32_t*)gh, t->st.p, t->tb);
         GBPE_LAUNCH_CHECK(t->ctx);
     } else if (t->u16)
-        hipLaunchKernelGGL(k_count_full<uint16_t>, dim3(g), dim3(TPB), 0, s, t->st,
-                           (const uint16_t*)t->buf[t->cur], t->tb);
+        hipLaunchKernelGGL(k_count_full<uint16_t>, dim3(g), dim3(TPB), 0, s, t->st.p,
+                           (const uint16_t*)t->buf[t->cur].p, t->tb);
     else
-        hipLaunchKernelGGL(k_count_full<uint32_t>, dim3(g), dim3(TPB), 0, s, t->st,
-                           (const uint32_t*)t->buf[t->cur], t->tb);
+        hipLaunchKernelGGL(k_count_full<uint32_t>, dim3(g), dim3(TPB), 0, s, t->st.p,
+                           (const uint32_t*)t->buf[t->cur].p, t->tb);
     GBPE_LAUNCH_CHECK(t->ctx);
-    hipLaunchKernelGGL(k_clear_dirty_all, dim3(gbpe_div_up(t->tb.nblk, 256)), dim3(256), 0, s, t->st, t->tb);
+    hipLaunchKernelGGL(k_clear_dirty_all, dim3(gbpe_div_up(t->tb.nblk, 256)), dim3(256), 0, s, t->st.p, t->tb);
     GBPE_LAUNCH_CHECK(t->ctx);
     if (t->u16)
-        hipLaunchKernelGGL(k_refresh<uint16_t>, dim3(grid_blocks(t->ctx, t->tb.nblk, 4)), dim3(TPB), 0, s, t->st, 0u,
+        hipLaunchKernelGGL(k_refresh<uint16_t>, dim3(grid_blocks(t->ctx, t->tb.nblk, 4)), dim3(TPB), 0, s, t->st.p, 0u,
                            0, t->tb, (uint16_t*)nullptr, (const uint32_t*)nullptr, (DevState*)nullptr);
     else
-        hipLaunchKernelGGL(k_refresh<uint32_t>, dim3(grid_blocks(t->ctx, t->tb.nblk, 4)), dim3(TPB), 0, s, t->st, 0u,
+        hipLaunchKernelGGL(k_refresh<uint32_t>, dim3(grid_blocks(t->ctx, t->tb.nblk, 4)), dim3(TPB), 0, s, t->st.p, 0u,
                            0, t->tb, (uint32_t*)nullptr, (const uint32_t*)nullptr, (DevState*)nullptr);
     GBPE_LAUNCH_CHECK(t->ctx);
     return GBPE_OK;
@@ -279,53 +252,42 @@ __global__ __launch_bounds__(TPB) void k_rehash(const uint2* __restrict__ old, u
 
 int table_rehash(gbpe_trainer* t, uint32_t lg) {
     hipStream_t s = t->ctx->stream;
-    uint2* old = t->tb.slots;
+    GbpeArray<uint2> old = std::move(t->tb_slots);   // kept until the live entries have moved
     const uint64_t nold = (uint64_t)t->tb.mask + 1;
-    t->tb.slots = nullptr;   // kept until the live entries have moved
     int rc = table_resize(t, lg);
-    if (rc != GBPE_OK) {
-        pool_free(t->ctx, old);
-        return rc;
-    }
-    const uint64_t slots = (uint64_t)t->tb.mask + 1;
-    TR_HIP(t, hipMemsetAsync(t->tb.slots, 0, slots * sizeof(uint2), s));
-    TR_HIP(t, hipMemsetAsync(t->tb.bmax, 0, (uint64_t)t->tb.nblk * sizeof(uint64_t), s));
-    TR_HIP(t, hipMemsetAsync(t->tb.bmax2, 0, (uint64_t)t->tb.nblk * sizeof(uint64_t), s));
-    TR_HIP(t, hipMemsetAsync(t->tb.blive, 0, (uint64_t)t->tb.nblk * sizeof(uint32_t), s));
-    TR_HIP(t, hipMemsetAsync(&t->st->used, 0, sizeof(uint32_t), s));
+    if (rc == GBPE_OK) rc = table_clear(t);
+    if (rc != GBPE_OK) return rc;
     hipLaunchKernelGGL(k_rehash, dim3(grid_persistent(t->ctx, gbpe_div_up(nold, TPB), 4)), dim3(TPB), 0, s,
-                       (const uint2*)old, nold, t->st, t->tb);
+                       (const uint2*)old.p, nold, t->st.p, t->tb);
     GBPE_LAUNCH_CHECK(t->ctx);
-    hipLaunchKernelGGL(k_clear_dirty_all, dim3(gbpe_div_up(t->tb.nblk, 256)), dim3(256), 0, s, t->st, t->tb);
+    hipLaunchKernelGGL(k_clear_dirty_all, dim3(gbpe_div_up(t->tb.nblk, 256)), dim3(256), 0, s, t->st.p, t->tb);
     // block maxima and the per-workgroup partial maxima the next selection reads
     if (t->u16)
-        GBPE_LAUNCH_REFRESH(uint16_t, t->g_refresh, t->tb.nblk, s, t->st, 0u, 0, t->tb, (uint16_t*)nullptr,
-                            (const uint32_t*)nullptr, (DevState*)nullptr, (uint32_t*)nullptr, FusedSel(), t->part,
+        GBPE_LAUNCH_REFRESH(uint16_t, t->g_refresh, t->tb.nblk, s, t->st.p, 0u, 0, t->tb, (uint16_t*)nullptr,
+                            (const uint32_t*)nullptr, (DevState*)nullptr, (uint32_t*)nullptr, FusedSel(), t->part.p,
                             (uint32_t*)nullptr);
     else
-        GBPE_LAUNCH_REFRESH(uint32_t, t->g_refresh, t->tb.nblk, s, t->st, 0u, 0, t->tb, (uint32_t*)nullptr,
-                            (const uint32_t*)nullptr, (DevState*)nullptr, (uint32_t*)nullptr, FusedSel(), t->part,
+        GBPE_LAUNCH_REFRESH(uint32_t, t->g_refresh, t->tb.nblk, s, t->st.p, 0u, 0, t->tb, (uint32_t*)nullptr,
+                            (const uint32_t*)nullptr, (DevState*)nullptr, (uint32_t*)nullptr, FusedSel(), t->part.p,
                             (uint32_t*)nullptr);
     GBPE_LAUNCH_CHECK(t->ctx);
     TR_HIP(t, hipStreamSynchronize(s));
-    pool_free(t->ctx, old);
     return GBPE_OK;
 }
 
 template <typename S>
 int launch_merge(gbpe_trainer* t, uint32_t round, hipStream_t s, uint32_t g_delta, uint32_t g_compact,
                  uint32_t g_refresh, bool timing, hipEvent_t* ev) {
-    S* cur = (S*)t->buf[t->cur ^ (round & 1)];
-    S* oth = (S*)t->buf[t->cur ^ (round & 1) ^ 1];
+    S* cur = (S*)t->buf[t->cur ^ (round & 1)].p;
+    S* oth = (S*)t->buf[t->cur ^ (round & 1) ^ 1].p;
     const bool exact = (t->flags & GBPE_TRAIN_EXACT_COMPACTION) != 0;
     if (timing) TR_HIP(t, hipEventRecord(ev[0], s));
-    hipLaunchKernelGGL(k_select, dim3(1), dim3(SEL_THREADS), 0, s, t->st, t->tb, t->d_log, t->grpsum,
+    hipLaunchKernelGGL(k_select, dim3(1), dim3(SEL_THREADS), 0, s, t->st.p, t->tb, t->d_log.p, t->grpsum.p,
                        (DevState*)nullptr, exact ? 1u : 0u);
     if (timing) TR_HIP(t, hipEventRecord(ev[1], s));
-    // many tiles: TPW tiles per k_delta workgroup (fewer hot-pair flushes)
+    // many tiles: 8 tiles per k_delta workgroup (fewer hot-pair flushes)
     const bool mt = t->delta_mt && g_delta >= t->delta_mt;
-    const uint32_t tpw = t->delta_tpw;
-    const uint32_t g_mt = (uint32_t)gbpe_div_up(g_delta, tpw);
+    const uint32_t g_mt = (uint32_t)gbpe_div_up(g_delta, 8);
     // stale-tail blocks (reference compaction): ~2K symbols each of the largest
     // possible tail (n/2), at most 1024
     const uint32_t g_mtail = exact ? 0u : (uint32_t)std::min<uint64_t>(1024, gbpe_div_up((uint64_t)t->n / 2 + 1, 2048));
@@ -333,33 +295,31 @@ int launch_merge(gbpe_trainer* t, uint32_t round, hipStream_t s, uint32_t g_delt
     const uint32_t g_dtail = exact ? 0u : (uint32_t)std::min<uint64_t>(1024, gbpe_div_up((uint64_t)t->n / 2 + 1, 1024));
     if (exact) {
         if (mt)
-            hipLaunchKernelGGL(tpw == 32 ? (k_delta_mt<S, true, 32>) : tpw == 16 ? (k_delta_mt<S, true, 16>) : (k_delta_mt<S, true, 8>),
-                               dim3(g_mt + g_mtail), dim3(TPB), 0, s, t->st, round, (const S*)cur, t->tb, t->hitmask,
-                               t->tile_cnt, t->grpsum, g_delta, g_mt, 0u, ZdrView());
+            hipLaunchKernelGGL((k_delta_mt<S, true, 8>), dim3(g_mt + g_mtail), dim3(TPB), 0, s, t->st.p, round,
+                               (const S*)cur, t->tb, t->hitmask.p, t->tile_cnt.p, t->grpsum.p, g_delta, g_mt, 0u, ZdrView());
         else
-            hipLaunchKernelGGL((k_delta<S, true>), dim3(g_delta), dim3(TPB), 0, s, t->st, round, (const S*)cur, t->tb,
-                               t->hitmask, t->tile_cnt, t->grpsum, g_delta, 0xFFFFFFFFu);
+            hipLaunchKernelGGL((k_delta<S, true>), dim3(g_delta), dim3(TPB), 0, s, t->st.p, round, (const S*)cur, t->tb,
+                               t->hitmask.p, t->tile_cnt.p, t->grpsum.p, g_delta, 0xFFFFFFFFu);
         if (timing) TR_HIP(t, hipEventRecord(ev[3], s));
-        hipLaunchKernelGGL((k_compact<S, true>), dim3(g_compact), dim3(CTPB), 0, s, t->st, round, cur, oth,
-                           (const uint32_t*)t->hitmask, (const uint32_t*)t->tile_cnt, (const uint32_t*)t->grpsum, t->tb);
+        hipLaunchKernelGGL((k_compact<S, true>), dim3(g_compact), dim3(CTPB), 0, s, t->st.p, round, cur, oth,
+                           (const uint32_t*)t->hitmask.p, (const uint32_t*)t->tile_cnt.p, (const uint32_t*)t->grpsum.p, t->tb);
     } else {
         if (mt)
-            hipLaunchKernelGGL(tpw == 32 ? (k_delta_mt<S, false, 32>) : tpw == 16 ? (k_delta_mt<S, false, 16>) : (k_delta_mt<S, false, 8>),
-                               dim3(g_mt + g_mtail), dim3(TPB), 0, s, t->st, round, (const S*)cur, t->tb, t->hitmask,
-                               t->tile_cnt, t->grpsum, g_delta, g_mt, 0u, ZdrView());
+            hipLaunchKernelGGL((k_delta_mt<S, false, 8>), dim3(g_mt + g_mtail), dim3(TPB), 0, s, t->st.p, round,
+                               (const S*)cur, t->tb, t->hitmask.p, t->tile_cnt.p, t->grpsum.p, g_delta, g_mt, 0u, ZdrView());
         else
-            hipLaunchKernelGGL((k_delta<S, false>), dim3(g_delta + g_dtail), dim3(TPB), 0, s, t->st, round, (const S*)cur,
-                               t->tb, t->hitmask, t->tile_cnt, t->grpsum, g_delta, g_delta);
+            hipLaunchKernelGGL((k_delta<S, false>), dim3(g_delta + g_dtail), dim3(TPB), 0, s, t->st.p, round, (const S*)cur,
+                               t->tb, t->hitmask.p, t->tile_cnt.p, t->grpsum.p, g_delta, g_delta);
         if (timing) TR_HIP(t, hipEventRecord(ev[3], s));
-        hipLaunchKernelGGL((k_compact<S, false>), dim3(g_compact), dim3(CTPB), 0, s, t->st, round, cur, oth,
-                           (const uint32_t*)t->hitmask, (const uint32_t*)t->tile_cnt, (const uint32_t*)t->grpsum, t->tb);
+        hipLaunchKernelGGL((k_compact<S, false>), dim3(g_compact), dim3(CTPB), 0, s, t->st.p, round, cur, oth,
+                           (const uint32_t*)t->hitmask.p, (const uint32_t*)t->tile_cnt.p, (const uint32_t*)t->grpsum.p, t->tb);
     }
     if (timing) TR_HIP(t, hipEventRecord(ev[2], s));
     FusedSel fs;
     fs.log = nullptr;
-    fs.grpsum = t->grpsum;
+    fs.grpsum = t->grpsum.p;
     fs.exact = exact ? 1u : 0u;
-    GBPE_LAUNCH_REFRESH(S, g_refresh, t->tb.nblk, s, t->st, round, 1, t->tb, cur, (const uint32_t*)nullptr,
+    GBPE_LAUNCH_REFRESH(S, g_refresh, t->tb.nblk, s, t->st.p, round, 1, t->tb, cur, (const uint32_t*)nullptr,
                         (DevState*)nullptr, (uint32_t*)nullptr, fs, (uint64_t*)nullptr, (uint32_t*)nullptr);
     if (timing) TR_HIP(t, hipEventRecord(ev[4], s));
     GBPE_LAUNCH_CHECK(t->ctx);
@@ -373,7 +333,6 @@ struct SpGrid {
     uint32_t wpg = 16;    // bitmap words per k_body workgroup
     uint32_t sub = 1;     // k_body workgroups per bitmap word (wpg = 1)
     bool seg8 = false;    // zone segments of 8K symbols (1024 threads x 8), else 16K
-    uint32_t ztail = 0;   // stale-tail slice blocks of the multi-tile zone k_delta
     uint32_t zone1;   // zone workgroups inside k_body: 1 = zone_one, >= 2 = zone_seg segments, 0 = multi-tile passes
     int bt;       // k_body workgroup size (256 or 1024)
     bool pair = false;   // launches may run two merges (zone_one in the 256-thread form)
@@ -435,8 +394,8 @@ void launch_body(int bt, uint32_t grid, hipStream_t s, A... args) {
 
 template <typename S>
 int launch_merge_sparse(gbpe_trainer* t, uint32_t round, hipStream_t s, const SpGrid& g, bool timing, hipEvent_t* ev) {
-    S* zc = (S*)t->zbuf[t->zcur ^ (round & 1)];
-    S* zo = (S*)t->zbuf[t->zcur ^ (round & 1) ^ 1];
+    S* zc = (S*)t->zbuf[t->zcur ^ (round & 1)].p;
+    S* zo = (S*)t->zbuf[t->zcur ^ (round & 1) ^ 1].p;
     const bool exact = (t->flags & GBPE_TRAIN_EXACT_COMPACTION) != 0;
     if (timing) TR_HIP(t, hipEventRecord(ev[0], s));
     if (timing) TR_HIP(t, hipEventRecord(ev[1], s));   // selection runs inside k_body (sel_inline)
@@ -445,30 +404,30 @@ int launch_merge_sparse(gbpe_trainer* t, uint32_t round, hipStream_t s, const Sp
     const uint32_t gb = g.body + (g.zone1 ? g.zone1 : g.copy);
     const uint32_t z1 = g.zone1;   // k_body's own zone workgroups
     const int bt = inbody ? (g.seg8 ? 2049 : 2048) : g.bt;
-    SelShard sh = sel_single(t);
+    SelShard sh;
     sh.sub = g.sub;
     sh.k2 = g.pair ? 1u : 0u;
     sh.prej = t->pair_prej;
-    if ((uint64_t)g.body + 1 > t->wg_cap)   // k_body's per-workgroup byte counters (and the zone's after them)
+    if ((uint64_t)g.body + 1 > t->wg_bytes.cap)   // k_body's per-workgroup byte counters (and the zone's after them)
         return gbpe_set_error(t->ctx, GBPE_E_INTERNAL, "k_body grid (%u) above its byte counters (%llu)", g.body,
-                              (unsigned long long)t->wg_cap);
+                              (unsigned long long)t->wg_bytes.cap);
     // events: [1] k_body [3] zone k_delta + k_compact (multi-tile zone) [2] k_refresh [4]
     // k_body picks the zone buffers by the state's merge index (a paired launch runs two
     // merges); the multi-tile kernels below run one merge per launch, so round = index
-    S* zb0 = (S*)t->zbuf[t->zcur];
-    S* zb1 = (S*)t->zbuf[t->zcur ^ 1];
+    S* zb0 = (S*)t->zbuf[t->zcur].p;
+    S* zb1 = (S*)t->zbuf[t->zcur ^ 1].p;
     if (exact)
-        launch_body<S, true>(bt, gb, s, t->st, round, (S*)sp_body(t), t->sec, t->bits, t->W, g.wpg, t->sig, t->tb,
-                             g.body, zb1, (S*)t->wtmp, t->d_clog ? 1u : 0u, t->zst, zb0, z1,
-                             (const uint64_t*)t->part, g.refresh, t->d_log, t->grpsum, t->wg_bytes, t->tb, sh,
-                             sp_mul(t), (ZSegState*)t->zseg);
+        launch_body<S, true>(bt, gb, s, t->st.p, round, (S*)sp_body(t), t->sec.p, t->bits.p, t->W, g.wpg, t->sig.p, t->tb,
+                             g.body, zb1, (S*)t->wtmp.p, t->d_clog.p ? 1u : 0u, t->zst.p, zb0, z1,
+                             (const uint64_t*)t->part.p, g.refresh, t->d_log.p, t->grpsum.p, t->wg_bytes.p, t->tb, sh,
+                             sp_mul(t), (ZSegState*)t->zseg.p);
     else
-        launch_body<S, false>(bt, gb, s, t->st, round, (S*)sp_body(t), t->sec, t->bits, t->W, g.wpg, t->sig, t->tb,
-                              g.body, zb1, (S*)t->wtmp, t->d_clog ? 1u : 0u, t->zst, zb0, z1,
-                              (const uint64_t*)t->part, g.refresh, t->d_log, t->grpsum, t->wg_bytes, t->tb, sh,
-                              sp_mul(t), (ZSegState*)t->zseg);
+        launch_body<S, false>(bt, gb, s, t->st.p, round, (S*)sp_body(t), t->sec.p, t->bits.p, t->W, g.wpg, t->sig.p, t->tb,
+                              g.body, zb1, (S*)t->wtmp.p, t->d_clog.p ? 1u : 0u, t->zst.p, zb0, z1,
+                              (const uint64_t*)t->part.p, g.refresh, t->d_log.p, t->grpsum.p, t->wg_bytes.p, t->tb, sh,
+                              sp_mul(t), (ZSegState*)t->zseg.p);
     if (timing) TR_HIP(t, hipEventRecord(ev[3], s));
-    if (!g.zone1 && !exact && t->zdr_on && t->zdr_out) {
+    if (!g.zone1 && !exact) {
         // a zone of many tiles, reference compaction: tiles dump their deltas, k_churn
         // runs the stale window and tail, k_zdr adds each distinct pair once (train_dev.h)
         const bool mt = t->delta_mt && g.zdelta >= t->delta_mt;
@@ -476,72 +435,43 @@ int launch_merge_sparse(gbpe_trainer* t, uint32_t round, hipStream_t s, const Sp
         const uint32_t ntw = mt ? g_mt : g.zdelta;
         const uint32_t gch = (uint32_t)std::min<uint64_t>(ZDR_P, std::max<uint64_t>(1, gbpe_div_up(((uint32_t)t->n - t->h_st->B) / 5 + 1, 16384)));
         ZdrView zv;
-        zv.out = t->zdr_out;
-        zv.offs = t->zdr_offs;
-        zv.flag = t->zdr_flag;
+        zv.out = t->zdr_out.p;
+        zv.offs = t->zdr_offs.p;
+        zv.flag = t->zdr_flag.p;
         zv.ntile = ntw;
         zv.tag = (uint32_t)(t->done + round + 1);
         if (ntw > t->zdr_ntile) return gbpe_set_error(t->ctx, GBPE_E_INTERNAL, "zone delta dumps too small");
         if (mt)
-            hipLaunchKernelGGL((k_delta_mt<S, false, 8>), dim3(g_mt), dim3(TPB), 0, s, t->zst, round, (const S*)zc, t->tb,
-                               t->hitmask, t->tile_cnt, t->grpsum, g.zdelta, g_mt, 0u, zv);
+            hipLaunchKernelGGL((k_delta_mt<S, false, 8>), dim3(g_mt), dim3(TPB), 0, s, t->zst.p, round, (const S*)zc, t->tb,
+                               t->hitmask.p, t->tile_cnt.p, t->grpsum.p, g.zdelta, g_mt, 0u, zv);
         else
-            hipLaunchKernelGGL((k_delta<S, false, true>), dim3(g.zdelta), dim3(TPB), 0, s, t->zst, round, (const S*)zc,
-                               t->tb, t->hitmask, t->tile_cnt, t->grpsum, g.zdelta, g.zdelta, zv);
-        hipLaunchKernelGGL((k_compact<S, false, true>), dim3(g.zdelta), dim3(CTPB), 0, s, t->zst, round, zc, zo,
-                           (const uint32_t*)t->hitmask, (const uint32_t*)t->tile_cnt, (const uint32_t*)t->grpsum, t->tb,
-                           (const S*)t->wtmp, (const DevState*)t->st, 1u);
-        hipLaunchKernelGGL(k_churn<S>, dim3(gch), dim3(CH_BT), 0, s, t->zst, round, zc, zo, (const uint32_t*)t->hitmask,
-                           (const uint32_t*)t->grpsum, (const S*)t->wtmp, t->tb, zv, ntw);
-        hipLaunchKernelGGL(k_zdr, dim3(ZDR_P), dim3(TPB), 0, s, zv, ntw + gch, t->tb, t->zst, round);
+            hipLaunchKernelGGL((k_delta<S, false, true>), dim3(g.zdelta), dim3(TPB), 0, s, t->zst.p, round, (const S*)zc,
+                               t->tb, t->hitmask.p, t->tile_cnt.p, t->grpsum.p, g.zdelta, g.zdelta, zv);
+        hipLaunchKernelGGL((k_compact<S, false, true>), dim3(g.zdelta), dim3(CTPB), 0, s, t->zst.p, round, zc, zo,
+                           (const uint32_t*)t->hitmask.p, (const uint32_t*)t->tile_cnt.p, (const uint32_t*)t->grpsum.p, t->tb,
+                           (const S*)t->wtmp.p, (const DevState*)t->st.p, 1u);
+        hipLaunchKernelGGL(k_churn<S>, dim3(gch), dim3(CH_BT), 0, s, t->zst.p, round, zc, zo, (const uint32_t*)t->hitmask.p,
+                           (const uint32_t*)t->grpsum.p, (const S*)t->wtmp.p, t->tb, zv, ntw);
+        hipLaunchKernelGGL(k_zdr, dim3(ZDR_P), dim3(TPB), 0, s, zv, ntw + gch, t->tb, t->zst.p, round);
     } else if (!g.zone1) {
-        // a zone of many tiles (the lexicon loop's first merges): TPW tiles per
-        // workgroup and one flush of their hot pairs, as in the dense loop
-        const bool mt = t->delta_mt && g.zdelta >= t->delta_mt;
+        // ... exact compaction: the tiles add their deltas directly (8 tiles per workgroup
+        // and one flush of their hot pairs from delta_mt tiles up, as in the dense loop)
         const uint32_t g_mt = (uint32_t)gbpe_div_up(g.zdelta, 8);
-        if (exact && mt)
-            hipLaunchKernelGGL((k_delta_mt<S, true, 8>), dim3(g_mt), dim3(TPB), 0, s, t->zst, round, (const S*)zc, t->tb,
-                               t->hitmask, t->tile_cnt, t->grpsum, g.zdelta, g_mt);
-        else if (mt)
-            hipLaunchKernelGGL((k_delta_mt<S, false, 8>), dim3(g_mt + g.ztail), dim3(TPB), 0, s, t->zst, round,
-                               (const S*)zc, t->tb, t->hitmask, t->tile_cnt, t->grpsum, g.zdelta, g_mt);
-        else if (exact)
-            hipLaunchKernelGGL((k_delta<S, true, true>), dim3(g.zdelta), dim3(TPB), 0, s, t->zst, round, (const S*)zc,
-                               t->tb, t->hitmask, t->tile_cnt, t->grpsum, g.zdelta, 0xFFFFFFFFu);
-        else   // + stale-tail slice blocks: the zone's tail (<= mc <= zone/5) in ~2K-symbol slices
-            hipLaunchKernelGGL((k_delta<S, false, true>), dim3(g.zdelta + g.ztail), dim3(TPB), 0, s, t->zst, round,
-                               (const S*)zc, t->tb, t->hitmask, t->tile_cnt, t->grpsum, g.zdelta, g.zdelta);
-    }
-    if (!g.zone1 && !(!exact && t->zdr_on && t->zdr_out)) {
-        if (exact)
-            hipLaunchKernelGGL((k_compact<S, true, true>), dim3(g.zcompact), dim3(CTPB), 0, s, t->zst, round, zc, zo,
-                               (const uint32_t*)t->hitmask, (const uint32_t*)t->tile_cnt, (const uint32_t*)t->grpsum,
-                               t->tb, (const S*)t->wtmp, (const DevState*)t->st);
+        if (t->delta_mt && g.zdelta >= t->delta_mt)
+            hipLaunchKernelGGL((k_delta_mt<S, true, 8>), dim3(g_mt), dim3(TPB), 0, s, t->zst.p, round, (const S*)zc, t->tb,
+                               t->hitmask.p, t->tile_cnt.p, t->grpsum.p, g.zdelta, g_mt);
         else
-            hipLaunchKernelGGL((k_compact<S, false, true>), dim3(g.zcompact), dim3(CTPB), 0, s, t->zst, round, zc, zo,
-                               (const uint32_t*)t->hitmask, (const uint32_t*)t->tile_cnt, (const uint32_t*)t->grpsum,
-                               t->tb, (const S*)t->wtmp, (const DevState*)t->st);
+            hipLaunchKernelGGL((k_delta<S, true, true>), dim3(g.zdelta), dim3(TPB), 0, s, t->zst.p, round, (const S*)zc,
+                               t->tb, t->hitmask.p, t->tile_cnt.p, t->grpsum.p, g.zdelta, 0xFFFFFFFFu);
+        hipLaunchKernelGGL((k_compact<S, true, true>), dim3(g.zcompact), dim3(CTPB), 0, s, t->zst.p, round, zc, zo,
+                           (const uint32_t*)t->hitmask.p, (const uint32_t*)t->tile_cnt.p, (const uint32_t*)t->grpsum.p,
+                           t->tb, (const S*)t->wtmp.p, (const DevState*)t->st.p);
     }
     if (timing) TR_HIP(t, hipEventRecord(ev[2], s));
-    GBPE_LAUNCH_REFRESH(S, g.refresh, t->tb.nblk, s, t->st, round, 2, t->tb, (S*)nullptr, (const uint32_t*)nullptr,
-                        t->zst, t->d_clog, FusedSel(), t->part, t->zseg);
+    GBPE_LAUNCH_REFRESH(S, g.refresh, t->tb.nblk, s, t->st.p, round, 2, t->tb, (S*)nullptr, (const uint32_t*)nullptr,
+                        t->zst.p, t->d_clog.p, FusedSel(), t->part.p, t->zseg.p);
     if (timing) TR_HIP(t, hipEventRecord(ev[4], s));
     GBPE_LAUNCH_CHECK(t->ctx);
-    return GBPE_OK;
-}
-
-template <typename T>
-int sp_grow(gbpe_trainer* t, T** p, uint64_t* cap, uint64_t need) {
-    if (*p && *cap >= need) return GBPE_OK;
-    pool_free(t->ctx, *p);
-    *p = nullptr;
-    *cap = 0;
-    if (pool_malloc(t->ctx, (void**)p, need * sizeof(T)) != hipSuccess) {
-        *p = nullptr;
-        return gbpe_set_error(t->ctx, GBPE_E_OOM, "hipMalloc(sparse layout, %llu B) failed",
-                              (unsigned long long)(need * sizeof(T)));
-    }
-    *cap = need;
     return GBPE_OK;
 }
 
@@ -555,20 +485,22 @@ __global__ void k_restride(const uint32_t* __restrict__ old, uint32_t w_old, uin
     }
 }
 
-// grow-and-copy a device array to `want` elements (the first `keep` kept)
-template <typename T>
-int sp_regrow(gbpe_trainer* t, T** p, uint64_t* cap, uint64_t want, uint64_t keep) {
-    if (*p && *cap >= want) return GBPE_OK;
-    T* nb = nullptr;
-    if (pool_malloc(t->ctx, (void**)&nb, want * sizeof(T)) != hipSuccess)
-        return gbpe_set_error(t->ctx, GBPE_E_OOM, "hipMalloc(sparse layout growth, %llu B) failed",
-                              (unsigned long long)(want * sizeof(T)));
+// the per-sector scratch and its scan block totals, for `cap` sectors
+int sp_scratch(gbpe_trainer* t, uint64_t cap) {
+    TR_HIP(t, t->sp_loc.reserve(t->ctx, cap));
+    TR_HIP(t, t->sp_blk.reserve(t->ctx, gbpe_div_up(cap, SCAN_BLK) + 1));
+    return GBPE_OK;
+}
+
+// one byte counter per k_body workgroup of a W-word bitmap row (at most body_cap of
+// them: body_grid) + the zone's, kept across entries (summed by gbpe_trainer_stats_get):
+// the old counters stay, the new ones start at 0
+int sp_wg_bytes(gbpe_trainer* t, uint64_t W) {
     hipStream_t s = t->ctx->stream;
-    if (*p && keep) TR_HIP(t, hipMemcpyAsync(nb, *p, keep * sizeof(T), hipMemcpyDeviceToDevice, s));
-    TR_HIP(t, hipStreamSynchronize(s));
-    pool_free(t->ctx, *p);
-    *p = nb;
-    *cap = want;
+    const uint64_t need = std::max<uint64_t>(gbpe_div_up(W, SP_WPW_MIN), t->body_cap) + 2, had = t->wg_bytes.cap;
+    if (need <= had) return GBPE_OK;
+    TR_HIP(t, t->wg_bytes.reserve_keep(t->ctx, need, had, s));
+    TR_HIP(t, hipMemsetAsync(t->wg_bytes.p + had, 0, (need - had) * sizeof(uint64_t), s));
     return GBPE_OK;
 }
 
@@ -578,82 +510,45 @@ int sp_regrow(gbpe_trainer* t, T** p, uint64_t* cap, uint64_t want, uint64_t kee
 // worst case of every zone shrink (C4's hand-over root: 64 GB of bitmap)
 int sp_reserve(gbpe_trainer* t, uint64_t need_sec, uint64_t need_store, uint64_t need_occ) {
     hipStream_t s = t->ctx->stream;
-    if (need_sec > t->nsec_cap || need_sec > (uint64_t)t->W * 32 || need_sec * SP_SIGW > t->sig_cap ||
-        need_sec > t->loc_cap) {
-        uint64_t cap = std::max<uint64_t>(need_sec, t->nsec_cap + t->nsec_cap / 2);
+    if (need_sec > t->sec.cap || need_sec > (uint64_t)t->W * 32 || need_sec * SP_SIGW > t->sig.cap ||
+        need_sec > t->sp_loc.cap || (t->lex && need_sec > t->lx_w0.cap)) {
+        uint64_t cap = std::max<uint64_t>(need_sec, t->sec.cap + t->sec.cap / 2);
         cap = (cap + 31) & ~31ull;
         const uint64_t keep = t->nsec;
-        int rc = sp_regrow(t, &t->sec, &t->nsec_cap, cap, keep);
-        if (rc == GBPE_OK) rc = sp_regrow(t, &t->sig, &t->sig_cap, cap * SP_SIGW, keep * SP_SIGW);
-        if (rc == GBPE_OK && t->lx_w0) {
-            uint64_t wcap = 0;   // (allocated with the sector capacity)
-            rc = sp_regrow(t, &t->lx_w0, &wcap, cap, keep);
-        }
+        TR_HIP(t, t->sec.reserve_keep(t->ctx, cap, keep, s));
+        TR_HIP(t, t->sig.reserve_keep(t->ctx, cap * SP_SIGW, keep * SP_SIGW, s));
+        if (t->lx_w0.p) TR_HIP(t, t->lx_w0.reserve_keep(t->ctx, cap, keep, s));
+        if (keep < cap) TR_HIP(t, hipMemsetAsync(t->sig.p + keep * SP_SIGW, 0, (cap - keep) * SP_SIGW * 4, s));
+        int rc = sp_scratch(t, cap);
         if (rc != GBPE_OK) return rc;
-        if (keep * SP_SIGW < cap * SP_SIGW)
-            TR_HIP(t, hipMemsetAsync(t->sig + keep * SP_SIGW, 0, (cap - keep) * SP_SIGW * 4, s));
-        pool_free(t->ctx, t->sp_loc);
-        pool_free(t->ctx, t->sp_blk);
-        t->sp_loc = nullptr;
-        t->sp_blk = nullptr;
-        t->loc_cap = 0;
-        if (pool_malloc(t->ctx, &t->sp_loc, cap * 4) != hipSuccess ||
-            pool_malloc(t->ctx, &t->sp_blk, (gbpe_div_up(cap, SCAN_BLK) + 1) * 8) != hipSuccess)
-            return gbpe_set_error(t->ctx, GBPE_E_OOM, "hipMalloc(sector scratch) failed");
-        t->loc_cap = cap;
         const uint32_t w_new = (uint32_t)gbpe_div_up(cap, 32);
-        if (w_new > t->W || !t->bits) {
-            uint32_t* nb = nullptr;
+        if (w_new > t->W || !t->bits.p) {
+            GbpeArray<uint32_t> nb;
             const uint64_t words = (uint64_t)t->max_id * w_new;
-            if (pool_malloc(t->ctx, &nb, words * 4) != hipSuccess)
-                return gbpe_set_error(t->ctx, GBPE_E_OOM, "hipMalloc(token bitmap, %llu B) failed",
-                                      (unsigned long long)(words * 4));
-            if (t->bits && t->W)
+            TR_HIP(t, nb.reserve(t->ctx, words));
+            if (t->bits.p && t->W)
                 hipLaunchKernelGGL(k_restride, dim3(grid_persistent(t->ctx, gbpe_div_up(words, 256), 8)), dim3(256), 0, s,
-                                   (const uint32_t*)t->bits, t->W, nb, w_new, (uint64_t)t->max_id);
+                                   (const uint32_t*)t->bits.p, t->W, nb.p, w_new, (uint64_t)t->max_id);
             else
-                TR_HIP(t, hipMemsetAsync(nb, 0, words * 4, s));
+                TR_HIP(t, hipMemsetAsync(nb.p, 0, words * 4, s));
             GBPE_LAUNCH_CHECK(t->ctx);
             TR_HIP(t, hipStreamSynchronize(s));
-            pool_free(t->ctx, t->bits);
-            t->bits = nb;
-            t->bits_cap = words;
+            t->bits = std::move(nb);
             t->W = w_new;
         }
-        // one byte counter per k_body workgroup (at most body_cap of them: body_grid) + the zone's
-        const uint64_t wneed = std::max<uint64_t>(gbpe_div_up(w_new, SP_WPW_MIN), t->body_cap) + 2;
-        if (t->wg_bytes && wneed > t->wg_cap) {
-            uint64_t* nb = nullptr;
-            TR_HIP(t, pool_malloc(t->ctx, &nb, wneed * sizeof(uint64_t)));
-            TR_HIP(t, hipMemsetAsync(nb, 0, wneed * sizeof(uint64_t), s));
-            TR_HIP(t, hipMemcpyAsync(nb, t->wg_bytes, t->wg_cap * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-            TR_HIP(t, hipStreamSynchronize(s));
-            pool_free(t->ctx, t->wg_bytes);
-            t->wg_bytes = nb;
-            t->wg_cap = wneed;
+        if (t->wg_bytes.p) {
+            rc = sp_wg_bytes(t, w_new);
+            if (rc != GBPE_OK) return rc;
         }
     }
-    if (t->lx_store && need_store > t->lx_cap) {
-        const uint64_t want = std::max<uint64_t>(need_store, t->lx_cap + t->lx_cap / 2);
-        uint64_t c1 = t->lx_cap, c2 = t->lx_cap;
-        void* st = t->lx_store;
-        if (pool_malloc(t->ctx, &t->lx_store, want * t->bps) != hipSuccess) {
-            t->lx_store = st;
-            return gbpe_set_error(t->ctx, GBPE_E_OOM, "hipMalloc(word lexicon growth) failed");
-        }
-        TR_HIP(t, hipMemcpyAsync(t->lx_store, st, t->lx_len * t->bps, hipMemcpyDeviceToDevice, s));
-        TR_HIP(t, hipStreamSynchronize(s));
-        pool_free(t->ctx, st);
-        int rc = sp_regrow(t, &t->lx_mul, &c1, want, t->lx_len);
-        if (rc != GBPE_OK) return rc;
-        (void)c2;
-        t->lx_cap = want;
+    if (t->lx_store.p && need_store > t->lx_store.cap) {
+        const uint64_t want = std::max<uint64_t>(need_store, t->lx_store.cap + t->lx_store.cap / 2);
+        TR_HIP(t, t->lx_store.reserve_keep(t->ctx, want, t->lx_len, s, t->bps));
+        TR_HIP(t, t->lx_mul.reserve_keep(t->ctx, want, t->lx_len, s));
     }
-    if (t->lx_occ && need_occ > t->lx_occ_cap) {
-        const uint64_t want = std::max<uint64_t>(need_occ, t->lx_occ_cap + t->lx_occ_cap / 2);
-        int rc = sp_regrow(t, &t->lx_occ, &t->lx_occ_cap, want, t->lx_nocc);
-        if (rc != GBPE_OK) return rc;
-    }
+    if (t->lx_occ.p && need_occ > t->lx_occ.cap)
+        TR_HIP(t, t->lx_occ.reserve_keep(t->ctx, std::max<uint64_t>(need_occ, t->lx_occ.cap + t->lx_occ.cap / 2),
+                                         t->lx_nocc, s));
     return GBPE_OK;
 }
 
@@ -662,24 +557,24 @@ int sp_reserve(gbpe_trainer* t, uint64_t need_sec, uint64_t need_store, uint64_t
 template <typename S>
 int sp_add_sectors(gbpe_trainer* t, uint32_t base, uint32_t len) {
     hipStream_t s = t->ctx->stream;
-    const uint32_t nw = (uint32_t)gbpe_div_up(len, t->sp_secw);
+    const uint32_t nw = (uint32_t)gbpe_div_up(len, SP_SECW);
     {
         int rc = sp_reserve(t, (uint64_t)t->nsec + nw, 0, 0);
         if (rc != GBPE_OK) return rc;
     }
-    const S* body = (const S*)t->buf[t->bcur];
+    const S* body = (const S*)t->buf[t->bcur].p;
     hipLaunchKernelGGL(k_sp_sectors<S>, dim3((uint32_t)gbpe_div_up(nw, TPB / 64)), dim3(TPB), 0, s, body, base, len,
-                       t->sp_secw, t->sp_loc, nw);
-    hipLaunchKernelGGL(k_sp_sector_len, dim3((uint32_t)gbpe_div_up(nw, 256)), dim3(256), 0, s, (const uint32_t*)t->sp_loc,
-                       nw, base + len, t->sec + t->nsec);
+                       SP_SECW, t->sp_loc.p, nw);
+    hipLaunchKernelGGL(k_sp_sector_len, dim3((uint32_t)gbpe_div_up(nw, 256)), dim3(256), 0, s, (const uint32_t*)t->sp_loc.p,
+                       nw, base + len, t->sec.p + t->nsec);
     if (t->nsec == 0) {   // a fresh build (sp_enter): whole columns
         hipLaunchKernelGGL(k_sp_bits<S>, dim3((uint32_t)gbpe_div_up(nw, TPB / 64)), dim3(TPB), 0, s, body,
-                           (const uint2*)t->sec, 0u, nw, (uint32_t*)nullptr, t->W, t->sig);
+                           (const uint2*)t->sec.p, 0u, nw, (uint32_t*)nullptr, t->W, t->sig.p);
         hipLaunchKernelGGL(k_sp_colbits<S>, dim3((uint32_t)gbpe_div_up(nw, 32)), dim3(TPB), 0, s, body,
-                           (const uint2*)t->sec, nw, t->bits, t->W);
+                           (const uint2*)t->sec.p, nw, t->bits.p, t->W);
     } else {
         hipLaunchKernelGGL(k_sp_bits<S>, dim3((uint32_t)gbpe_div_up(nw, TPB / 64)), dim3(TPB), 0, s, body,
-                           (const uint2*)t->sec, t->nsec, nw, t->bits, t->W, t->sig);
+                           (const uint2*)t->sec.p, t->nsec, nw, t->bits.p, t->W, t->sig.p);
     }
     GBPE_LAUNCH_CHECK(t->ctx);
     t->nsec += nw;
@@ -693,11 +588,11 @@ template <typename S>
 int sp_filters(gbpe_trainer* t, bool with_bits) {
     hipStream_t s = t->ctx->stream;
     hipLaunchKernelGGL(k_sp_bits<S>, dim3((uint32_t)gbpe_div_up(t->nsec, TPB / 64)), dim3(TPB), 0, s,
-                       (const S*)sp_body(t), (const uint2*)t->sec, 0u, t->nsec, (uint32_t*)nullptr, t->W, t->sig);
+                       (const S*)sp_body(t), (const uint2*)t->sec.p, 0u, t->nsec, (uint32_t*)nullptr, t->W, t->sig.p);
     if (with_bits) {
-        TR_HIP(t, hipMemsetAsync(t->bits, 0, (uint64_t)t->max_id * t->W * 4, s));
+        TR_HIP(t, hipMemsetAsync(t->bits.p, 0, (uint64_t)t->max_id * t->W * 4, s));
         hipLaunchKernelGGL(k_sp_colbits<S>, dim3((uint32_t)gbpe_div_up(t->nsec, 32)), dim3(TPB), 0, s,
-                           (const S*)sp_body(t), (const uint2*)t->sec, t->nsec, t->bits, t->W);
+                           (const S*)sp_body(t), (const uint2*)t->sec.p, t->nsec, t->bits.p, t->W);
     }
     GBPE_LAUNCH_CHECK(t->ctx);
     t->sp_age = 0;
@@ -718,20 +613,6 @@ struct LxCarve {
         return reinterpret_cast<T*>(base + b);
     }
 };
-
-int lx_scratch(gbpe_trainer* t, uint64_t bytes) {
-    if (t->lx_tmp && t->lx_tmp_bytes >= bytes) return GBPE_OK;
-    TR_HIP(t, hipStreamSynchronize(t->ctx->stream));
-    pool_free(t->ctx, t->lx_tmp);
-    t->lx_tmp = nullptr;
-    t->lx_tmp_bytes = 0;
-    if (pool_malloc(t->ctx, &t->lx_tmp, bytes) != hipSuccess) {
-        t->lx_tmp = nullptr;
-        return gbpe_set_error(t->ctx, GBPE_E_OOM, "hipMalloc(lexicon scratch, %llu B) failed", (unsigned long long)bytes);
-    }
-    t->lx_tmp_bytes = bytes;
-    return GBPE_OK;
-}
 
 // exclusive scan of n u32 counts in place (k_chunk_scan1/2); blk gets n/SCAN_BLK + 2
 // entries, the total at blk[nblk]
@@ -762,14 +643,12 @@ int lx_analyze(gbpe_trainer* t, const S* seg, uint32_t len, bool fresh, LxPlan& 
     const uint64_t ntiles = gbpe_div_up(len, TILE);
     // word count first (sizes the scratch); the tile counts live outside the
     // scratch, which may move, so k_lx_wpos uses them as they are
-    uint32_t* tc = nullptr;
-    uint64_t* tb = nullptr;
-    auto tc_free = gbpe_scope_exit([&] {
-        pool_free(t->ctx, tc);
-        pool_free(t->ctx, tb);
-    });
-    TR_HIP(t, pool_malloc(t->ctx, &tc, (ntiles + 64) * 4));
-    TR_HIP(t, pool_malloc(t->ctx, &tb, (ntiles / SCAN_BLK + 4) * 8));
+    GbpeArray<uint32_t> tc_own;
+    GbpeArray<uint64_t> tb_own;
+    TR_HIP(t, tc_own.reserve(t->ctx, ntiles + 64));
+    TR_HIP(t, tb_own.reserve(t->ctx, ntiles / SCAN_BLK + 4));
+    uint32_t* tc = tc_own.p;
+    uint64_t* tb = tb_own.p;
     hipLaunchKernelGGL(k_lx_count<S>, dim3((uint32_t)ntiles), dim3(TPB), 0, s, seg, len, tc);
     lx_scan(s, tc, ntiles, tb);
     GBPE_LAUNCH_CHECK(t->ctx);
@@ -797,9 +676,9 @@ int lx_analyze(gbpe_trainer* t, const S* seg, uint32_t len, bool fresh, LxPlan& 
     const uint64_t need = 9ull * (nw + 64) * 4 + Pfull * 16 + (nbbf + 64) * 4 +
                           2 * (nbbf / SCAN_BLK + (uint64_t)nw / SCAN_BLK + 8) * 8 + 32 * 256 +
                           (two ? nwg_max * LX2_LT * sizeof(LxSlot) + 2 * nwg_max * 256 * 4 + 1024 : 0);
-    int rc = lx_scratch(t, need);
-    if (rc != GBPE_OK) return rc;
-    LxCarve c{(char*)t->lx_tmp};
+    TR_HIP(t, t->lx_tmp.reserve(t->ctx, need));
+    int rc = GBPE_OK;
+    LxCarve c{(char*)t->lx_tmp.p};
     lp.wpos = c.take<uint32_t>(nw + 1);
     uint32_t* otmp = c.take<uint32_t>(nw + 1);
     uint32_t* longs = c.take<uint32_t>(nw + 1);
@@ -849,7 +728,7 @@ int lx_analyze(gbpe_trainer* t, const S* seg, uint32_t len, bool fresh, LxPlan& 
     };
     uint64_t P = Pfull;
     constexpr uint32_t LX_SAMPLE = 1u << 22;   // words of the sample
-    if (nw > 4u * LX_SAMPLE && t->lx_size_on) {
+    if (nw > 4u * LX_SAMPLE) {
         rc = hash_pass(2ull * LX_SAMPLE, LX_SAMPLE);
         if (rc != GBPE_OK) return rc;
         if (!h[1]) {   // distinct words grow slower than words (Heaps): D ~ d (nw / sample)^0.8, at <= 1/3 load
@@ -890,9 +769,9 @@ int lx_analyze(gbpe_trainer* t, const S* seg, uint32_t len, bool fresh, LxPlan& 
     if (fresh && T * 2 > len) return GBPE_OK;   // not worth it: the store would be more than half the body
     if (nw) {
         // the entries' compact copy (the store's layout) for the occurrence check
-        S* rstore = nullptr;
-        auto rs_free = gbpe_scope_exit([&] { pool_free(t->ctx, rstore); });
-        TR_HIP(t, pool_malloc(t->ctx, &rstore, (T + 1) * sizeof(S)));
+        GbpeArray<S> rs_own;
+        TR_HIP(t, rs_own.reserve(t->ctx, T + 1));
+        S* rstore = rs_own.p;
         if (lp.nu)
             hipLaunchKernelGGL(k_lx_fill<S>, dim3((uint32_t)gbpe_div_up(lp.nu, 256)), dim3(256), 0, s, seg,
                                (const uint32_t*)lp.urep, (const uint32_t*)lp.usz, (const uint32_t*)lp.umul,
@@ -918,7 +797,7 @@ int lx_analyze(gbpe_trainer* t, const S* seg, uint32_t len, bool fresh, LxPlan& 
 template <typename S>
 int lx_commit(gbpe_trainer* t, LxPlan& lp, const S* seg, bool fresh, bool keep_occ = true) {
     hipStream_t s = t->ctx->stream;
-    const uint32_t SEC = t->sp_secw;
+    const uint32_t SEC = SP_SECW;
     const uint64_t sbase = gbpe_div_up(t->lx_len, SEC) * SEC;
     const uint64_t nwin = gbpe_div_up(lp.T ? lp.T : 1, SEC);
     const uint64_t kb = sbase / SEC;
@@ -926,32 +805,32 @@ int lx_commit(gbpe_trainer* t, LxPlan& lp, const S* seg, bool fresh, bool keep_o
         int rc = sp_reserve(t, kb + nwin, sbase + nwin * SEC, keep_occ ? t->lx_nocc + lp.nw : 0);
         if (rc != GBPE_OK) return rc;
     }
-    S* store = (S*)t->lx_store;
+    S* store = (S*)t->lx_store.p;
     if (sbase > t->lx_len) {   // alignment padding: separators no sector covers
         TR_HIP(t, hipMemsetAsync(store + t->lx_len, 0, (sbase - t->lx_len) * sizeof(S), s));
-        TR_HIP(t, hipMemsetAsync(t->lx_mul + t->lx_len, 0, (sbase - t->lx_len) * 4, s));
+        TR_HIP(t, hipMemsetAsync(t->lx_mul.p + t->lx_len, 0, (sbase - t->lx_len) * 4, s));
     }
     const uint32_t* upre = lp.upre;
     if (lp.nu) {
         hipLaunchKernelGGL(k_lx_fill<S>, dim3((uint32_t)gbpe_div_up(lp.nu, 256)), dim3(256), 0, s, seg,
                            (const uint32_t*)lp.urep, (const uint32_t*)lp.usz, (const uint32_t*)lp.umul, upre,
-                           (const uint64_t*)lp.ublk, lp.nu, store + sbase, t->lx_mul + sbase);
-        TR_HIP(t, hipMemsetAsync(t->sp_loc, 0xFF, nwin * 4, s));
+                           (const uint64_t*)lp.ublk, lp.nu, store + sbase, t->lx_mul.p + sbase);
+        TR_HIP(t, hipMemsetAsync(t->sp_loc.p, 0xFF, nwin * 4, s));
         hipLaunchKernelGGL(k_lx_secstart, dim3((uint32_t)gbpe_div_up(lp.nu, 256)), dim3(256), 0, s, upre,
-                           (const uint64_t*)lp.ublk, lp.nu, SEC, (uint32_t)sbase, t->lx_nuid, t->sp_loc, t->lx_w0 + kb);
+                           (const uint64_t*)lp.ublk, lp.nu, SEC, (uint32_t)sbase, t->lx_nuid, t->sp_loc.p, t->lx_w0.p + kb);
         hipLaunchKernelGGL(k_sp_sector_len, dim3((uint32_t)gbpe_div_up(nwin, 256)), dim3(256), 0, s,
-                           (const uint32_t*)t->sp_loc, (uint32_t)nwin, (uint32_t)(sbase + lp.T), t->sec + kb);
+                           (const uint32_t*)t->sp_loc.p, (uint32_t)nwin, (uint32_t)(sbase + lp.T), t->sec.p + kb);
     } else {
-        TR_HIP(t, hipMemsetAsync(t->sec + kb, 0, nwin * sizeof(uint2), s));
+        TR_HIP(t, hipMemsetAsync(t->sec.p + kb, 0, nwin * sizeof(uint2), s));
     }
     if (lp.nw && keep_occ)
-        TR_HIP(t, hipMemcpyAsync(t->lx_occ + t->lx_nocc, lp.occ, (uint64_t)lp.nw * 4, hipMemcpyDeviceToDevice, s));
+        TR_HIP(t, hipMemcpyAsync(t->lx_occ.p + t->lx_nocc, lp.occ, (uint64_t)lp.nw * 4, hipMemcpyDeviceToDevice, s));
     // token bits and signatures of the new sectors (a fresh build: whole columns)
     hipLaunchKernelGGL(k_sp_bits<S>, dim3((uint32_t)gbpe_div_up(nwin, TPB / 64)), dim3(TPB), 0, s, (const S*)store,
-                       (const uint2*)t->sec, (uint32_t)kb, (uint32_t)nwin, fresh ? (uint32_t*)nullptr : t->bits, t->W, t->sig);
+                       (const uint2*)t->sec.p, (uint32_t)kb, (uint32_t)nwin, fresh ? (uint32_t*)nullptr : t->bits.p, t->W, t->sig.p);
     if (fresh)
         hipLaunchKernelGGL(k_sp_colbits<S>, dim3((uint32_t)gbpe_div_up(nwin, 32)), dim3(TPB), 0, s, (const S*)store,
-                           (const uint2*)t->sec, (uint32_t)nwin, t->bits, t->W);
+                           (const uint2*)t->sec.p, (uint32_t)nwin, t->bits.p, t->W);
     GBPE_LAUNCH_CHECK(t->ctx);
     t->nsec = (uint32_t)(kb + nwin);
     t->lx_len = sbase + lp.T;
@@ -969,11 +848,10 @@ template <typename S>
 int lx_expand(gbpe_trainer* t, S* dst, uint64_t dst_cap, uint64_t* tot, const uint32_t* occ = nullptr, uint64_t n_occ = 0) {
     // occ: another occurrence list over this store (the lexicon hand-over's rank lists)
     hipStream_t s = t->ctx->stream;
-    if (!occ) occ = t->lx_occ, n_occ = t->lx_nocc;
+    if (!occ) occ = t->lx_occ.p, n_occ = t->lx_nocc;
     const uint64_t nu = t->lx_nuid, no = n_occ;
-    int rc = lx_scratch(t, (2 * nu + no + 64) * 4 + (no / SCAN_BLK + 8) * 8 + 4096);
-    if (rc != GBPE_OK) return rc;
-    LxCarve c{(char*)t->lx_tmp};
+    TR_HIP(t, t->lx_tmp.reserve(t->ctx, (2 * nu + no + 64) * 4 + (no / SCAN_BLK + 8) * 8 + 4096));
+    LxCarve c{(char*)t->lx_tmp.p};
     uint32_t* coff = c.take<uint32_t>(nu + 1);
     uint32_t* clen = c.take<uint32_t>(nu + 1);
     uint32_t* olen = c.take<uint32_t>(no + 1);
@@ -982,7 +860,7 @@ int lx_expand(gbpe_trainer* t, S* dst, uint64_t dst_cap, uint64_t* tot, const ui
     TR_HIP(t, hipMemsetAsync(bad, 0, 4, s));
     if (t->nsec)
         hipLaunchKernelGGL(k_lx_wordpos<S>, dim3((uint32_t)gbpe_div_up(t->nsec, TPB / 64)), dim3(TPB), 0, s,
-                           (const S*)t->lx_store, (const uint2*)t->sec, t->nsec, (const uint32_t*)t->lx_w0, coff, clen);
+                           (const S*)t->lx_store.p, (const uint2*)t->sec.p, t->nsec, (const uint32_t*)t->lx_w0.p, coff, clen);
     if (no)
         hipLaunchKernelGGL(k_lx_olen, dim3((uint32_t)gbpe_div_up(no, 256)), dim3(256), 0, s, occ, no,
                            (const uint32_t*)clen, olen, (uint32_t)nu, bad);
@@ -1000,7 +878,7 @@ int lx_expand(gbpe_trainer* t, S* dst, uint64_t dst_cap, uint64_t* tot, const ui
                               (unsigned long long)total, (unsigned long long)dst_cap);
     if (no)
         hipLaunchKernelGGL(k_lx_expand<S>, dim3((uint32_t)gbpe_div_up(no, 256)), dim3(256), 0, s, occ, no,
-                           (const uint32_t*)coff, (const uint32_t*)clen, (const S*)t->lx_store, (const uint32_t*)olen,
+                           (const uint32_t*)coff, (const uint32_t*)clen, (const S*)t->lx_store.p, (const uint32_t*)olen,
                            (const uint64_t*)oblk, dst, (uint32_t)nu);
     GBPE_LAUNCH_CHECK(t->ctx);
     return GBPE_OK;
@@ -1012,20 +890,16 @@ int lx_expand(gbpe_trainer* t, S* dst, uint64_t dst_cap, uint64_t* tot, const ui
 template <typename S>
 int lx_check(gbpe_trainer* t, const S* cur, uint32_t Zs, const LxPlan& lp) {
     hipStream_t s = t->ctx->stream;
-    S* chk = nullptr;
-    auto chk_free = gbpe_scope_exit([&] { pool_free(t->ctx, chk); });   // every return path, TR_HIP's included
-    if (pool_malloc(t->ctx, &chk, ((uint64_t)Zs + 64) * sizeof(S)) != hipSuccess) {
-        chk = nullptr;
-        return gbpe_set_error(t->ctx, GBPE_E_OOM, "lex_check: hipMalloc(%u symbols) failed", Zs);
-    }
+    GbpeArray<S> chk;
+    TR_HIP(t, chk.reserve(t->ctx, (uint64_t)Zs + 64));
     uint64_t tot = 0;
-    const int rc = lx_expand<S>(t, chk, (uint64_t)Zs + 64, &tot);
+    const int rc = lx_expand<S>(t, chk.p, (uint64_t)Zs + 64, &tot);
     TR_HIP(t, hipStreamSynchronize(s));
     if (rc != GBPE_OK) return rc;   // nothing was written to chk
     std::vector<S> a(Zs), b(Zs);
     // (the expansion may be shorter than the body: compare what it wrote, report the rest through `expanded`)
     const uint64_t ncmp = std::min<uint64_t>(tot, Zs);
-    TR_HIP(t, hipMemcpy(a.data(), chk, ncmp * sizeof(S), hipMemcpyDeviceToHost));
+    TR_HIP(t, hipMemcpy(a.data(), chk.p, ncmp * sizeof(S), hipMemcpyDeviceToHost));
     TR_HIP(t, hipMemcpy(b.data(), cur, (uint64_t)Zs * sizeof(S), hipMemcpyDeviceToHost));
     uint64_t bad = ncmp < Zs ? ncmp : Zs;
     for (uint64_t i = 0; i < ncmp; ++i)
@@ -1035,8 +909,8 @@ int lx_check(gbpe_trainer* t, const S* cur, uint32_t Zs, const LxPlan& lp) {
         }
     std::vector<uint32_t> mm(lp.T);
     std::vector<S> ss(lp.T);
-    TR_HIP(t, hipMemcpy(mm.data(), t->lx_mul, (uint64_t)lp.T * 4, hipMemcpyDeviceToHost));
-    TR_HIP(t, hipMemcpy(ss.data(), t->lx_store, (uint64_t)lp.T * sizeof(S), hipMemcpyDeviceToHost));
+    TR_HIP(t, hipMemcpy(mm.data(), t->lx_mul.p, (uint64_t)lp.T * 4, hipMemcpyDeviceToHost));
+    TR_HIP(t, hipMemcpy(ss.data(), t->lx_store.p, (uint64_t)lp.T * sizeof(S), hipMemcpyDeviceToHost));
     uint64_t wsum = 0, nz = 0, badm = 0;
     for (uint32_t i = 0; i < lp.T; ++i) {
         wsum += mm[i];
@@ -1061,46 +935,26 @@ int lx_check(gbpe_trainer* t, const S* cur, uint32_t Zs, const LxPlan& lp) {
 // row), pair signatures — bitmap and signatures zeroed
 int sp_alloc_layout(gbpe_trainer* t, uint64_t cap) {
     hipStream_t s = t->ctx->stream;
-    int rc = sp_grow(t, &t->sec, &t->nsec_cap, cap);
-    if (rc == GBPE_OK && (!t->sp_loc || t->loc_cap < cap)) {
-        pool_free(t->ctx, t->sp_loc);
-        pool_free(t->ctx, t->sp_blk);
-        t->sp_loc = nullptr;
-        t->sp_blk = nullptr;
-        t->loc_cap = 0;
-        if (pool_malloc(t->ctx, &t->sp_loc, cap * 4) != hipSuccess ||
-            pool_malloc(t->ctx, &t->sp_blk, (gbpe_div_up(cap, SCAN_BLK) + 1) * 8) != hipSuccess)
-            rc = gbpe_set_error(t->ctx, GBPE_E_OOM, "hipMalloc(sector scratch) failed");
-        else
-            t->loc_cap = cap;
-    }
+    TR_HIP(t, t->sec.reserve(t->ctx, cap));
+    int rc = sp_scratch(t, cap);
     if (rc != GBPE_OK) return rc;
     t->W = (uint32_t)gbpe_div_up(cap, 32);
-    rc = sp_grow(t, &t->bits, &t->bits_cap, (uint64_t)t->max_id * t->W);
-    if (rc == GBPE_OK) rc = sp_grow(t, &t->sig, &t->sig_cap, cap * SP_SIGW);
-    if (rc != GBPE_OK) return rc;
+    TR_HIP(t, t->bits.reserve(t->ctx, (uint64_t)t->max_id * t->W));
+    TR_HIP(t, t->sig.reserve(t->ctx, cap * SP_SIGW));
     t->nsec = 0;
-    TR_HIP(t, hipMemsetAsync(t->bits, 0, (uint64_t)t->max_id * t->W * 4, s));
-    TR_HIP(t, hipMemsetAsync(t->sig, 0, cap * SP_SIGW * 4, s));
+    TR_HIP(t, hipMemsetAsync(t->bits.p, 0, (uint64_t)t->max_id * t->W * 4, s));
+    TR_HIP(t, hipMemsetAsync(t->sig.p, 0, cap * SP_SIGW * 4, s));
     return GBPE_OK;
 }
 
-// word-lexicon store for `cap` sectors of sp_secw symbols, occurrence list of `ocap`
+// word-lexicon store for `cap` sectors of SP_SECW symbols, occurrence list of `ocap`
 int sp_alloc_lexicon(gbpe_trainer* t, uint64_t cap, uint64_t ocap) {
-    const uint64_t scap = cap * t->sp_secw;
-    if (!t->lx_store || t->lx_cap < scap) {
-        pool_free(t->ctx, t->lx_store);
-        pool_free(t->ctx, t->lx_mul);
-        pool_free(t->ctx, t->lx_w0);
-        t->lx_store = nullptr;
-        t->lx_mul = t->lx_w0 = nullptr;
-        t->lx_cap = 0;
-        if (pool_malloc(t->ctx, &t->lx_store, scap * t->bps) != hipSuccess || pool_malloc(t->ctx, &t->lx_mul, scap * 4) != hipSuccess ||
-            pool_malloc(t->ctx, &t->lx_w0, cap * 4) != hipSuccess)
-            return gbpe_set_error(t->ctx, GBPE_E_OOM, "hipMalloc(word lexicon) failed");
-        t->lx_cap = scap;
-    }
-    return sp_grow(t, &t->lx_occ, &t->lx_occ_cap, ocap);
+    const uint64_t scap = cap * SP_SECW;
+    TR_HIP(t, t->lx_store.reserve(t->ctx, scap, t->bps));
+    TR_HIP(t, t->lx_mul.reserve(t->ctx, scap));
+    TR_HIP(t, t->lx_w0.reserve(t->ctx, cap));
+    TR_HIP(t, t->lx_occ.reserve(t->ctx, ocap));
+    return GBPE_OK;
 }
 
 // zone buffers (zeroed): the zone, and the stale source (previous stream,
@@ -1111,39 +965,21 @@ int sp_alloc_zone(gbpe_trainer* t, uint64_t z, uint64_t prev_mc) {
     uint64_t zneed = (gbpe_div_up(z + prev_mc + 1, TILE) + 2) * TILE;
     const uint64_t zmin = (uint64_t)(t->u16 ? zone_max<uint16_t>(1024) : zone_max<uint32_t>(1024)) + TILE;
     if (zneed < zmin) zneed = zmin;
-    if (zneed > t->zcap) {
-        for (int k = 0; k < 2; ++k) {
-            pool_free(t->ctx, t->zbuf[k]);
-            t->zbuf[k] = nullptr;
-        }
-        pool_free(t->ctx, t->wtmp);
-        t->wtmp = nullptr;
-        t->zcap = 0;
-        if (pool_malloc(t->ctx, &t->zbuf[0], zneed * t->bps) != hipSuccess || pool_malloc(t->ctx, &t->zbuf[1], zneed * t->bps) != hipSuccess ||
-            pool_malloc(t->ctx, &t->wtmp, zneed * t->bps) != hipSuccess)
-            return gbpe_set_error(t->ctx, GBPE_E_OOM, "hipMalloc(zone) failed");
-        t->zcap = zneed;
-    }
+    for (GbpeArray<void>* b : {&t->zbuf[0], &t->zbuf[1], &t->wtmp}) TR_HIP(t, b->reserve(t->ctx, zneed, t->bps));
     {   // delta dumps of the multi-tile zone passes: the most tile workgroups a pass can have
-        const uint64_t zt = gbpe_div_up(t->zcap, TILE);
+        const uint64_t zt = gbpe_div_up(t->zbuf[0].cap, TILE);
         const uint32_t need = (uint32_t)std::max<uint64_t>(std::min<uint64_t>(zt, t->delta_mt ? t->delta_mt : zt),
                                                            gbpe_div_up(zt, 8)) + 1;
-        if (t->zdr_on && need > t->zdr_ntile) {
-            pool_free(t->ctx, t->zdr_out);
-            pool_free(t->ctx, t->zdr_offs);
-            pool_free(t->ctx, t->zdr_flag);
-            t->zdr_out = nullptr, t->zdr_offs = nullptr, t->zdr_flag = nullptr;
-            t->zdr_ntile = 0;
+        if (need > t->zdr_ntile) {
             const uint64_t nd = (uint64_t)need + ZDR_P;
-            if (pool_malloc(t->ctx, &t->zdr_out, ((uint64_t)need * ZDR_N_TILE + (uint64_t)ZDR_P * ZDR_N_CHURN) * sizeof(uint2)) !=
-                    hipSuccess ||
-                pool_malloc(t->ctx, &t->zdr_offs, nd * (ZDR_P + 1) * 4) != hipSuccess || pool_malloc(t->ctx, &t->zdr_flag, nd * 4) != hipSuccess)
-                return gbpe_set_error(t->ctx, GBPE_E_OOM, "hipMalloc(zone delta dumps) failed");
-            TR_HIP(t, hipMemsetAsync(t->zdr_flag, 0, nd * 4, s));   // tags start at 1
+            TR_HIP(t, t->zdr_out.reserve(t->ctx, (uint64_t)need * ZDR_N_TILE + (uint64_t)ZDR_P * ZDR_N_CHURN));
+            TR_HIP(t, t->zdr_offs.reserve(t->ctx, nd * (ZDR_P + 1)));
+            TR_HIP(t, t->zdr_flag.reserve(t->ctx, nd));
+            TR_HIP(t, hipMemsetAsync(t->zdr_flag.p, 0, nd * 4, s));   // tags start at 1
             t->zdr_ntile = need;
         }
     }
-    for (int k = 0; k < 2; ++k) TR_HIP(t, hipMemsetAsync(t->zbuf[k], 0, t->zcap * t->bps, s));
+    for (int k = 0; k < 2; ++k) TR_HIP(t, hipMemsetAsync(t->zbuf[k].p, 0, t->zbuf[k].cap * t->bps, s));
     return GBPE_OK;
 }
 
@@ -1153,13 +989,11 @@ int sp_alloc_zone(gbpe_trainer* t, uint64_t z, uint64_t prev_mc) {
 // k_refresh (block maxima + partial maxima) before the first sparse merge.
 int sp_init_states(gbpe_trainer* t, uint64_t cap, uint32_t Zs, uint32_t z, uint32_t zlast) {
     hipStream_t s = t->ctx->stream;
-    if (!t->zst) {
-        TR_HIP(t, pool_malloc(t->ctx, &t->zst, sizeof(DevState)));
-        TR_HIP(t, pool_hmalloc(t->ctx, &t->h_zst, sizeof(DevState)));
-    }
-    memset(t->h_zst, 0, sizeof(DevState));
+    TR_HIP(t, t->zst.reserve(t->ctx, 1));
+    TR_HIP(t, t->h_zst.reserve(t->ctx, 1));
+    memset(t->h_zst.p, 0, sizeof(DevState));
     t->h_zst->n = z;
-    TR_HIP(t, hipMemcpyAsync(t->zst, t->h_zst, sizeof(DevState), hipMemcpyHostToDevice, s));
+    TR_HIP(t, hipMemcpyAsync(t->zst.p, t->h_zst.p, sizeof(DevState), hipMemcpyHostToDevice, s));
     t->h_st->B = Zs;
     t->h_st->Bp = Zs;
     t->h_st->body_rm = 0;
@@ -1171,31 +1005,20 @@ int sp_init_states(gbpe_trainer* t, uint64_t cap, uint32_t Zs, uint32_t z, uint3
     t->h_st->is_last = z ? 1u : 0u;
     TR_HIP(t, hipMemcpyAsync(&t->st->zlast, &t->h_st->zlast, sizeof(uint32_t), hipMemcpyHostToDevice, s));
     TR_HIP(t, hipMemcpyAsync(&t->st->is_last, &t->h_st->is_last, sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    {   // one byte counter per k_body workgroup, kept across entries (summed by gbpe_trainer_stats_get)
-        const uint64_t need = std::max<uint64_t>(gbpe_div_up(gbpe_div_up(cap, 32), SP_WPW_MIN), t->body_cap) + 2;
-        if (need > t->wg_cap) {
-            uint64_t* nb = nullptr;
-            TR_HIP(t, pool_malloc(t->ctx, &nb, need * sizeof(uint64_t)));
-            TR_HIP(t, hipMemsetAsync(nb, 0, need * sizeof(uint64_t), s));
-            if (t->wg_bytes) TR_HIP(t, hipMemcpyAsync(nb, t->wg_bytes, t->wg_cap * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-            TR_HIP(t, hipStreamSynchronize(s));
-            pool_free(t->ctx, t->wg_bytes);
-            t->wg_bytes = nb;
-            t->wg_cap = need;
-        }
-    }
+    int rc = sp_wg_bytes(t, gbpe_div_up(cap, 32));
+    if (rc != GBPE_OK) return rc;
     // the zone rule's last count (sel_inline): the count of the merge before entry
     TR_HIP(t, hipMemcpyAsync(&t->st->mc_prev, &t->st->mc, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
     // per-k_refresh-workgroup maxima the sparse merges select from (sel_inline)
-    if (!t->part) {
-        int rc = part_alloc(t);
+    if (!t->part.p) {
+        rc = part_reserve(t);
         if (rc != GBPE_OK) return rc;
     }
-    if (!t->zseg) {
-        TR_HIP(t, pool_malloc(t->ctx, &t->zseg, sizeof(ZSegState)));
-        TR_HIP(t, hipMemsetAsync(t->zseg, 0, sizeof(ZSegState), t->ctx->stream));
+    if (!t->zseg.p) {
+        TR_HIP(t, t->zseg.reserve(t->ctx, gbpe_div_up(sizeof(ZSegState), 4)));
+        TR_HIP(t, hipMemsetAsync(t->zseg.p, 0, sizeof(ZSegState), s));
     }
-    if (!t->d_u32) TR_HIP(t, pool_malloc(t->ctx, &t->d_u32, 64));
+    TR_HIP(t, t->d_u32.reserve(t->ctx, 16));
     return GBPE_OK;
 }
 
@@ -1212,17 +1035,17 @@ int sp_enter(gbpe_trainer* t, bool with_zone = true, uint32_t next_mc = 0) {
     const uint64_t prev_mc = t->last_mc;   // the previous stream is n + prev_mc long
     const uint64_t nmc = next_mc ? next_mc : prev_mc;
     const uint64_t zt = std::max<uint64_t>((uint64_t)t->sp_zt * nmc, 2ull * nmc + prev_mc) + 64;
-    const S* cur = (const S*)t->buf[t->cur];
-    const S* stale = (const S*)t->buf[t->cur ^ 1];
-    if (!t->d_u32) TR_HIP(t, pool_malloc(t->ctx, &t->d_u32, 64));
+    const S* cur = (const S*)t->buf[t->cur].p;
+    const S* stale = (const S*)t->buf[t->cur ^ 1].p;
+    TR_HIP(t, t->d_u32.reserve(t->ctx, 16));
     uint32_t Zs = n;
     if (with_zone) {
         if (zt + 2 >= n) return GBPE_OK;
-        hipLaunchKernelGGL(k_sp_zone_start<S>, dim3(1), dim3(1024), 0, s, cur, (uint32_t)(n - zt), t->d_u32);
+        hipLaunchKernelGGL(k_sp_zone_start<S>, dim3(1), dim3(1024), 0, s, cur, (uint32_t)(n - zt), t->d_u32.p);
         GBPE_LAUNCH_CHECK(t->ctx);
-        TR_HIP(t, hipMemcpyAsync(&Zs, t->d_u32, 4, hipMemcpyDeviceToHost, s));
+        TR_HIP(t, hipMemcpyAsync(&Zs, t->d_u32.p, 4, hipMemcpyDeviceToHost, s));
         TR_HIP(t, hipStreamSynchronize(s));
-        if (Zs < t->sp_secw) return GBPE_OK;   // the whole stream is one long word (or tiny): stay dense
+        if (Zs < SP_SECW) return GBPE_OK;   // the whole stream is one long word (or tiny): stay dense
     }
     const uint32_t z = n - Zs;
     // word lexicon: plan the deduplicated body first; it sizes the sectors
@@ -1239,8 +1062,8 @@ int sp_enter(gbpe_trainer* t, bool with_zone = true, uint32_t next_mc = 0) {
     // sector capacity: windows over [0, n) (the lexicon: over its store, with room
     // for a 16th of the zone's symbols as the words shrinks append; sp_reserve grows
     // it) plus one partial window per zone shrink (at most SP_SHRINKS per entry)
-    const uint64_t cap = lp.ok ? gbpe_div_up((uint64_t)lp.T + z / 16, t->sp_secw) + 2 * (SP_SHRINKS + 1)
-                               : gbpe_div_up(n, t->sp_secw) + SP_SHRINKS + 1;
+    const uint64_t cap = lp.ok ? gbpe_div_up((uint64_t)lp.T + z / 16, SP_SECW) + 2 * (SP_SHRINKS + 1)
+                               : gbpe_div_up(n, SP_SECW) + SP_SHRINKS + 1;
     int rc = sp_alloc_layout(t, cap);
     if (rc != GBPE_OK) return rc;
     t->bcur = t->cur;
@@ -1261,16 +1084,16 @@ int sp_enter(gbpe_trainer* t, bool with_zone = true, uint32_t next_mc = 0) {
     rc = sp_alloc_zone(t, z, prev_mc);
     if (rc != GBPE_OK) return rc;
     if (z) {
-        TR_HIP(t, hipMemcpyAsync(t->zbuf[0], cur + Zs, (uint64_t)z * t->bps, hipMemcpyDeviceToDevice, s));
+        TR_HIP(t, hipMemcpyAsync(t->zbuf[0].p, cur + Zs, (uint64_t)z * t->bps, hipMemcpyDeviceToDevice, s));
         uint64_t sl = (uint64_t)z + prev_mc;
         if (Zs + sl > t->cap_syms) sl = t->cap_syms - Zs;
-        if (sl > t->zcap) sl = t->zcap;
-        TR_HIP(t, hipMemcpyAsync(t->zbuf[1], stale + Zs, sl * t->bps, hipMemcpyDeviceToDevice, s));
+        if (sl > t->zbuf[0].cap) sl = t->zbuf[0].cap;
+        TR_HIP(t, hipMemcpyAsync(t->zbuf[1].p, stale + Zs, sl * t->bps, hipMemcpyDeviceToDevice, s));
     }
     rc = sp_init_states(t, cap, Zs, z, z);
     if (rc != GBPE_OK) return rc;
-    GBPE_LAUNCH_REFRESH(S, t->g_refresh, t->tb.nblk, s, t->st, 0u, 0, t->tb, (S*)nullptr, (const uint32_t*)nullptr,
-                        (DevState*)nullptr, (uint32_t*)nullptr, FusedSel(), t->part, (uint32_t*)nullptr);
+    GBPE_LAUNCH_REFRESH(S, t->g_refresh, t->tb.nblk, s, t->st.p, 0u, 0, t->tb, (S*)nullptr, (const uint32_t*)nullptr,
+                        (DevState*)nullptr, (uint32_t*)nullptr, FusedSel(), t->part.p, (uint32_t*)nullptr);
     GBPE_LAUNCH_CHECK(t->ctx);
     TR_HIP(t, hipStreamSynchronize(s));
     t->sp = true;
@@ -1289,20 +1112,20 @@ int sp_enter(gbpe_trainer* t, bool with_zone = true, uint32_t next_mc = 0) {
 template <typename S>
 int sp_shrink(gbpe_trainer* t) {
     hipStream_t s = t->ctx->stream;
-    DevState* hs = t->h_st;
+    DevState* hs = t->h_st.p;
     const uint32_t z = (uint32_t)t->n - hs->B;
     const uint64_t zt = (uint64_t)t->sp_zt * t->last_mc + 64;
     // paired launches run in the zone_one form: a zone just above it whose target fits
     // shrinks into it (else it stays there until z >= 2 zt + 4096: 1 GiB merges ~12K-25K)
     const uint64_t zmax1 = zone_max<S>(256);
     const bool to_one = t->pair_on && t->pair_one && z > zmax1 && zt + 512 <= zmax1;
-    if (t->sp_shrinks >= SP_SHRINKS_MAX || ((uint64_t)z < zt * t->shrink_pct / 100 + 4096 && !to_one)) return GBPE_OK;
-    S* zc = (S*)t->zbuf[t->zcur];
-    S* zo = (S*)t->zbuf[t->zcur ^ 1];
-    hipLaunchKernelGGL(k_sp_zone_start<S>, dim3(1), dim3(1024), 0, s, (const S*)zc, (uint32_t)(z - zt), t->d_u32);
+    if (t->sp_shrinks >= SP_SHRINKS_MAX || ((uint64_t)z < zt * SP_SHRINK_PCT / 100 + 4096 && !to_one)) return GBPE_OK;
+    S* zc = (S*)t->zbuf[t->zcur].p;
+    S* zo = (S*)t->zbuf[t->zcur ^ 1].p;
+    hipLaunchKernelGGL(k_sp_zone_start<S>, dim3(1), dim3(1024), 0, s, (const S*)zc, (uint32_t)(z - zt), t->d_u32.p);
     GBPE_LAUNCH_CHECK(t->ctx);
     uint32_t L = 0;
-    TR_HIP(t, hipMemcpyAsync(&L, t->d_u32, 4, hipMemcpyDeviceToHost, s));
+    TR_HIP(t, hipMemcpyAsync(&L, t->d_u32.p, 4, hipMemcpyDeviceToHost, s));
     TR_HIP(t, hipStreamSynchronize(s));
     if (L < (to_one ? 512u : 4096u)) return GBPE_OK;
     if (t->lex) {   // the front's words join the lexicon (deduplicated among themselves)
@@ -1313,7 +1136,7 @@ int sp_shrink(gbpe_trainer* t) {
         if (!lp.ok) return GBPE_OK;   // (a collision or no room): the zone keeps its front this time
     } else {
         if ((uint64_t)t->bend + L > t->cap_syms) return GBPE_OK;
-        S* body = (S*)t->buf[t->bcur];
+        S* body = (S*)t->buf[t->bcur].p;
         TR_HIP(t, hipMemcpyAsync(body + t->bend, zc, (uint64_t)L * t->bps, hipMemcpyDeviceToDevice, s));
         int rc = sp_add_sectors<S>(t, t->bend, L);
         if (rc != GBPE_OK) return rc;
@@ -1322,12 +1145,12 @@ int sp_shrink(gbpe_trainer* t) {
     // and the stale buffer, which the next window reads below the previous zone
     // length (<= z + last_mc); the buffers' capacity is the zone at entry (~200M
     // symbols at 1 GiB), so moving all of it cost ~1 ms per late shrink.
-    const uint64_t live = std::min<uint64_t>(t->zcap, (uint64_t)z + 2ull * t->last_mc + 2ull * TILE);
+    const uint64_t live = std::min<uint64_t>(t->zbuf[0].cap, (uint64_t)z + 2ull * t->last_mc + 2ull * TILE);
     const uint64_t rest = live - L;
-    TR_HIP(t, hipMemcpyAsync(t->wtmp, zc + L, rest * t->bps, hipMemcpyDeviceToDevice, s));
-    TR_HIP(t, hipMemcpyAsync(zc, t->wtmp, rest * t->bps, hipMemcpyDeviceToDevice, s));
-    TR_HIP(t, hipMemcpyAsync(t->wtmp, zo + L, rest * t->bps, hipMemcpyDeviceToDevice, s));
-    TR_HIP(t, hipMemcpyAsync(zo, t->wtmp, rest * t->bps, hipMemcpyDeviceToDevice, s));
+    TR_HIP(t, hipMemcpyAsync(t->wtmp.p, zc + L, rest * t->bps, hipMemcpyDeviceToDevice, s));
+    TR_HIP(t, hipMemcpyAsync(zc, t->wtmp.p, rest * t->bps, hipMemcpyDeviceToDevice, s));
+    TR_HIP(t, hipMemcpyAsync(t->wtmp.p, zo + L, rest * t->bps, hipMemcpyDeviceToDevice, s));
+    TR_HIP(t, hipMemcpyAsync(zo, t->wtmp.p, rest * t->bps, hipMemcpyDeviceToDevice, s));
     TR_HIP(t, hipMemsetAsync(zc + rest, 0, (uint64_t)L * t->bps, s));
     TR_HIP(t, hipMemsetAsync(zo + rest, 0, (uint64_t)L * t->bps, s));
     hs->B += L;
@@ -1350,36 +1173,36 @@ int sp_exit(gbpe_trainer* t) {
         return gbpe_set_error(t->ctx, GBPE_E_INTERNAL, "a trainer built from shard lexicons cannot return to one dense "
                               "stream (a merge outgrew the zone, or the stream was asked for: use gbpe_trainer_expand)");
     hipStream_t s = t->ctx->stream;
-    DevState* hs = t->h_st;
-    TR_HIP(t, hipMemcpyAsync(hs, t->st, sizeof(DevState), hipMemcpyDeviceToHost, s));
+    DevState* hs = t->h_st.p;
+    TR_HIP(t, hipMemcpyAsync(hs, t->st.p, sizeof(DevState), hipMemcpyDeviceToHost, s));
     TR_HIP(t, hipStreamSynchronize(s));
     const uint32_t B = hs->B, Bp = hs->Bp, n = hs->n;
     const uint32_t z = n - B;
-    S* body = (S*)t->buf[t->bcur];
-    S* dst = (S*)t->buf[t->bcur ^ 1];
+    S* body = (S*)t->buf[t->bcur].p;
+    S* dst = (S*)t->buf[t->bcur ^ 1].p;
     const uint32_t nsec = t->nsec;
     uint64_t btot = 0;
     if (t->lex) {
         int rc = lx_expand<S>(t, dst, (uint64_t)B, &btot);
         if (rc != GBPE_OK) return rc;
     } else {
-        hipLaunchKernelGGL(k_sp_counts, dim3((uint32_t)gbpe_div_up(nsec, 256)), dim3(256), 0, s, (const uint2*)t->sec, nsec,
-                           t->sp_loc);
+        hipLaunchKernelGGL(k_sp_counts, dim3((uint32_t)gbpe_div_up(nsec, 256)), dim3(256), 0, s, (const uint2*)t->sec.p, nsec,
+                           t->sp_loc.p);
         const uint64_t nblk = gbpe_div_up(nsec, SCAN_BLK);
-        hipLaunchKernelGGL(k_chunk_scan1, dim3((uint32_t)nblk), dim3(SCAN_TPB), 0, s, (const uint32_t*)t->sp_loc,
-                           (uint64_t)nsec, t->sp_loc, t->sp_blk);
-        hipLaunchKernelGGL(k_chunk_scan2, dim3(1), dim3(SCAN_TPB), 0, s, t->sp_blk, nblk, t->sp_blk + nblk);
+        hipLaunchKernelGGL(k_chunk_scan1, dim3((uint32_t)nblk), dim3(SCAN_TPB), 0, s, (const uint32_t*)t->sp_loc.p,
+                           (uint64_t)nsec, t->sp_loc.p, t->sp_blk.p);
+        hipLaunchKernelGGL(k_chunk_scan2, dim3(1), dim3(SCAN_TPB), 0, s, t->sp_blk.p, nblk, t->sp_blk.p + nblk);
         hipLaunchKernelGGL(k_sp_gather<S>, dim3((uint32_t)gbpe_div_up(nsec, TPB / 64)), dim3(TPB), 0, s, (const S*)body,
-                           (const uint2*)t->sec, nsec, (const uint32_t*)t->sp_loc, (const uint64_t*)t->sp_blk, dst);
+                           (const uint2*)t->sec.p, nsec, (const uint32_t*)t->sp_loc.p, (const uint64_t*)t->sp_blk.p, dst);
         GBPE_LAUNCH_CHECK(t->ctx);
-        TR_HIP(t, hipMemcpyAsync(&btot, t->sp_blk + nblk, 8, hipMemcpyDeviceToHost, s));
+        TR_HIP(t, hipMemcpyAsync(&btot, t->sp_blk.p + nblk, 8, hipMemcpyDeviceToHost, s));
     }
-    TR_HIP(t, hipMemcpyAsync(dst + B, t->zbuf[t->zcur], (uint64_t)z * t->bps, hipMemcpyDeviceToDevice, s));
+    TR_HIP(t, hipMemcpyAsync(dst + B, t->zbuf[t->zcur].p, (uint64_t)z * t->bps, hipMemcpyDeviceToDevice, s));
     // zero the rest of the dense buffer's padding the kernels may read (halo / look-ahead)
     TR_HIP(t, hipMemsetAsync(dst + n, 0, (t->cap_syms - n) * t->bps, s));
-    uint64_t sl = t->zcap;
+    uint64_t sl = t->zbuf[0].cap;
     if (Bp + sl > t->cap_syms) sl = t->cap_syms - Bp;
-    TR_HIP(t, hipMemcpyAsync(body + Bp, t->zbuf[t->zcur ^ 1], sl * t->bps, hipMemcpyDeviceToDevice, s));
+    TR_HIP(t, hipMemcpyAsync(body + Bp, t->zbuf[t->zcur ^ 1].p, sl * t->bps, hipMemcpyDeviceToDevice, s));
     hs->sp_abort = 0;
     TR_HIP(t, hipMemcpyAsync(&t->st->sp_abort, &hs->sp_abort, 4, hipMemcpyHostToDevice, s));
     TR_HIP(t, hipStreamSynchronize(s));
@@ -1434,12 +1257,12 @@ void trainer_config(gbpe_trainer* t, gbpe_ctx* ctx, const gbpe_train_opts* opts)
     t->body_sub = (uint32_t)std::min<long>(4, std::max<long>(1, gbpe_debug_knob("bsub", t->body_sub)));
     t->sub_k = (uint32_t)std::max<long>(1, gbpe_debug_knob("subk", t->sub_k));
     t->sub_zone = (uint32_t)std::max<long>(1, gbpe_debug_knob("subz", t->sub_zone));
-    if (t->sp_zt < t->zone_f) t->sp_zt = t->zone_f;
+    if (t->sp_zt < SP_ZONE_F) t->sp_zt = SP_ZONE_F;
     if (const char* e = getenv("GBPE_SPARSE_TRACE")) {
         t->trace = fopen(e, "w");
-        if (t->trace && (pool_malloc(t->ctx, &t->d_clog, (size_t)t->batch * 8) != hipSuccess ||
-                         pool_hmalloc(t->ctx, &t->h_clog, (size_t)t->batch * 8) != hipSuccess))
-            t->d_clog = nullptr, t->h_clog = nullptr;   // trace without candidate counts
+        if (t->trace && (t->d_clog.reserve(ctx, (size_t)t->batch * 2) != hipSuccess ||
+                         t->h_clog.reserve(ctx, (size_t)t->batch * 2) != hipSuccess))
+            t->d_clog.release(), t->h_clog.release();   // trace without candidate counts
     }
     t->bps = t->u16 ? 2 : 4;
 }
