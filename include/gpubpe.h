@@ -82,7 +82,15 @@ int gbpe_word_boundary(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, uint8_t*
 
 /* PreTokenizer.preTokenizeBytes (src/wasm/pre_tokenizer.mjs:459-509) word-start
  * mask for NFC UTF-8 bytes (the reference also NFC-normalises: identity on NFC
- * input).  Classes: Unicode general categories (unicode_classes.h). */
+ * input).  Classes: Unicode general categories (unicode_classes.h).
+ * Domain: well-formed UTF-8 that may be cut short at its end — every byte
+ * 0x80-0xBF is owned by the lead byte before it, by that lead's size (a cut
+ * sequence decodes with its missing bytes read as 0, as in the reference; a
+ * 4-byte sequence that decodes to 0x110000 or above has class Other).  A stray
+ * continuation byte is outside the domain: the reference starts a 4-byte
+ * codepoint at it, these kernels do not, and the result there is unspecified.
+ * The _device form takes device pointers of any alignment, reads only
+ * d_bytes[0, n) and writes only d_ws[0, n), on the context's stream. */
 int gbpe_pretokenize_gpt4(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, uint8_t* ws_out);
 int gbpe_pretokenize_gpt4_device(gbpe_ctx* ctx, const void* d_bytes, uint64_t n, void* d_ws);
 

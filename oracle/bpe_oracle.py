@@ -559,6 +559,12 @@ def gpt4_word_starts(data: bytes) -> np.ndarray:
     n = len(cps)
     starts = [0] * n
     starts[0] = 1
+    # run_start[k]: first codepoint of the digit run that holds codepoint k (the reference
+    # walks back from i - 1 at every digit, :209-215: the same index, without the walk)
+    run_start = list(range(n))
+    for k in range(1, n):
+        if cls[k] == PT_DIGIT and cls[k - 1] == PT_DIGIT:
+            run_start[k] = run_start[k - 1]
     i = 1
     while i < n:
         prev, curr = cls[i - 1], cls[i]
@@ -584,9 +590,7 @@ def gpt4_word_starts(data: bytes) -> np.ndarray:
             i += 1
             continue
         if curr == PT_DIGIT and prev == PT_DIGIT:
-            rs = i - 1
-            while rs > 0 and cls[rs - 1] == PT_DIGIT:
-                rs -= 1
+            rs = run_start[i - 1]
             if (i - rs) % 3 == 0:
                 starts[i] = 1
             i += 1
