@@ -51,7 +51,12 @@ __global__ __launch_bounds__(WALK_TPB) void k_trie_walk(const uint8_t* __restric
     auto byte_at = [&](uint64_t p) -> uint32_t {
         const uint64_t wi = p >> 2;
         if (wi != widx) {
-            word = in32[wi];
+            if (wi * 4 + 4 <= n) {
+                word = in32[wi];
+            } else {   // the last partial word: byte loads inside [0, n)
+                word = 0;
+                for (uint64_t j = wi * 4; j < n; ++j) word |= (uint32_t)in[j] << ((j & 3u) * 8u);
+            }
             widx = wi;
         }
         return (word >> ((p & 3u) * 8u)) & 0xFFu;
@@ -1264,8 +1269,8 @@ extern "C" int gbpe_encode_batch(gbpe_ctx* ctx, gbpe_trie* tr, const uint8_t* by
 extern "C" int gbpe_encode_device(gbpe_ctx* ctx, gbpe_trie* tr, const void* d_bytes, uint64_t n, uint32_t chunk_size,
                                   void* d_out, uint64_t out_cap, uint64_t* n_out) {
     if (!ctx || !tr || !n_out || (n && (!d_bytes || !d_out))) return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
-    if ((uintptr_t)d_bytes & 3u) return gbpe_set_error(ctx, GBPE_E_INVALID, "d_bytes must be 4-byte aligned");
     *n_out = 0;
+    if ((uintptr_t)d_bytes & 3u) return gbpe_set_error(ctx, GBPE_E_INVALID, "d_bytes must be 4-byte aligned");
     if (n == 0) return GBPE_OK;
     return encode_device_impl(ctx, tr, (const uint8_t*)d_bytes, n, effective_cs(tr, chunk_size), (uint32_t*)d_out,
                               out_cap, n_out);

@@ -317,10 +317,17 @@ int  gbpe_trie_info(const gbpe_trie* trie, uint32_t* n_records, uint32_t* max_to
 
 /* tokenizer.js:173-206 encodeBytes: chunked greedy longest match.
  * chunk_size 0 = the reference's adaptive size (tokenizer.js:67-68).
- * On GBPE_E_CAPACITY *n_out holds the required token count. */
+ * On GBPE_E_CAPACITY *n_out holds the required token count and nothing is written
+ * at or beyond out[out_cap] (tokens below it may or may not have been written). */
 int gbpe_encode(gbpe_ctx* ctx, gbpe_trie* trie, const uint8_t* bytes, uint64_t n, uint32_t chunk_size,
                 uint32_t* out, uint64_t out_cap, uint64_t* n_out);
-/* Device-resident variant: d_bytes / d_out are device pointers (bench path). */
+/* Device-resident variant: d_bytes / d_out are device pointers (bench path).
+ * d_bytes must be 4-byte aligned (any multiple of 4: the walks load 16 bytes at a
+ * time from dword-aligned addresses); otherwise GBPE_E_INVALID with *n_out = 0 and
+ * nothing launched.  Only d_bytes[0, n) is read: the last partial 16-byte block and
+ * the last partial word are loaded byte by byte.  d_out is 4-byte aligned (u32
+ * tokens).  On GBPE_E_CAPACITY *n_out holds the required token count, the first
+ * out_cap tokens are in d_out and nothing is written at or beyond d_out[out_cap]. */
 int gbpe_encode_device(gbpe_ctx* ctx, gbpe_trie* trie, const void* d_bytes, uint64_t n, uint32_t chunk_size,
                        void* d_out, uint64_t out_cap, uint64_t* n_out);
 /* Many documents in one call (no reference counterpart: tokenizer.js encodes one

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import bpe_oracle as O
+from encode_dev import BatchDev as _Dev
 
 pytestmark = pytest.mark.gpu
 
@@ -54,50 +55,6 @@ def _cut(text, lengths):
         p += ln
     assert p <= len(text)
     return docs
-
-
-class _Dev:
-    """Device buffers of one gbpe_encode_batch_device call."""
-
-    def __init__(self, eng, docs, out_cap=None, guard=0):
-        from gpubpe import _lib, flatten_documents
-        self.lib, self.ctx = _lib.load(), eng.device
-        self.buf, self.offs = flatten_documents(docs)
-        self.n, self.n_docs = int(self.buf.shape[0]), len(docs)
-        self.out_cap = self.n if out_cap is None else out_cap
-        self.guard = guard
-        self.ptrs = []
-        self.d_in = self._alloc(max(self.n, 1), self.buf)
-        self.d_off = self._alloc(8 * (self.n_docs + 1), self.offs)
-        self.d_tok_off = self._alloc(8 * (self.n_docs + 1), np.full(self.n_docs + 1, 0xEEEEEEEE, np.uint64))
-        self.d_out = self._alloc(4 * (self.out_cap + guard) + 4, np.full(self.out_cap + guard + 1, 0xA5A5A5A5, np.uint32))
-
-    def _alloc(self, nbytes, init):
-        from gpubpe import _lib
-        p = C.c_void_p()
-        _lib.check(self.lib.gbpe_device_alloc(self.ctx, nbytes, C.byref(p)), self.ctx, "alloc")
-        self.ptrs.append(p)
-        init = np.ascontiguousarray(init)
-        if init.nbytes:
-            _lib.check(self.lib.gbpe_memcpy_h2d(self.ctx, p, init.ctypes.data_as(C.c_void_p), init.nbytes), self.ctx, "h2d")
-        return p
-
-    def run(self, trie, cs):
-        n_out = C.c_uint64()
-        rc = self.lib.gbpe_encode_batch_device(self.ctx, trie, self.d_in, self.n, self.d_off, self.n_docs, cs, self.d_out,
-                                               self.out_cap, self.d_tok_off, C.byref(n_out))
-        return rc, int(n_out.value)
-
-    def fetch(self, ptr, count, dtype):
-        from gpubpe import _lib
-        host = np.empty(count, dtype=dtype)
-        if count:
-            _lib.check(self.lib.gbpe_memcpy_d2h(self.ctx, host.ctypes.data_as(C.c_void_p), ptr, host.nbytes), self.ctx, "d2h")
-        return host
-
-    def free(self):
-        for p in self.ptrs:
-            self.lib.gbpe_device_free(self.ctx, p)
 
 
 def _device_batch(eng, tok, docs):
