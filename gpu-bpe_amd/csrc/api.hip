@@ -39,6 +39,10 @@ static const char* const kKernelNames[] = {
     "k_trie_walk_batch",      // the walk from descriptors: k_trie_walk_v5_batch (packed double array) / k_trie_walk_batch
     "k_chunk_compact_batch",  // k_chunk_compact4_batch
     "k_doc_tok_off",          // per-document token offsets
+    // device decode (gbpe_decode*; replaces the host loop of tokenizer.js:344-363)
+    "k_dec_len",              // per-token byte lengths + their block-exclusive scan
+    "k_dec_scatter",          // the vocab bytes to their final offsets: k_dec_scatter (16-byte vectors) / k_dec_scatter_plain
+    "k_dec_doc_off",          // per-document byte offsets + the check of the token offsets
 };
 
 // ── context memory pool (common.h GbpePool) ───────────────────────────────
@@ -143,7 +147,7 @@ hipError_t gbpe_dev_malloc(gbpe_ctx* ctx, void** p, uint64_t bytes) {
 
 extern "C" {
 
-const char* gbpe_version(void) { return "gpubpe 0.7 (gfx950, abi 7)"; }
+const char* gbpe_version(void) { return "gpubpe 0.8 (gfx950, abi 8)"; }
 
 int gbpe_abi_version(void) { return GBPE_ABI_VERSION; }
 
@@ -196,6 +200,9 @@ void gbpe_ctx_destroy(gbpe_ctx* ctx) {
     hipFree(ctx->enc_in);
     hipFree(ctx->enc_out);
     hipFree(ctx->enc_docs);
+    hipFree(ctx->dec_in);
+    hipFree(ctx->dec_out);
+    hipFree(ctx->dec_work);
     hipFree(ctx->pt_agg);
     if (ctx->enc_host_total) hipHostFree(ctx->enc_host_total);
     if (pool_debug())

@@ -47,6 +47,11 @@ struct gbpe_ctx {
     void* enc_out = nullptr;      uint64_t enc_out_bytes = 0;
     void* enc_docs = nullptr;     uint64_t enc_docs_bytes = 0;   // gbpe_encode_batch: per-document table
     uint32_t* enc_host_total = nullptr;   // pinned, 64 bytes
+    // decode pool, grown the same way: token slice / byte slice of the host forms, prefixes + document offsets
+    void* dec_in = nullptr;       uint64_t dec_in_bytes = 0;
+    void* dec_out = nullptr;      uint64_t dec_out_bytes = 0;
+    void* dec_work = nullptr;     uint64_t dec_work_bytes = 0;
+    double dec_ms[3] = {0, 0, 0};
     void* pt_agg = nullptr;       uint64_t pt_agg_bytes = 0;   // pre-tokenizer block aggregates
     hipEvent_t ev[8] = {};
     double enc_ms[3] = {0, 0, 0};

@@ -110,6 +110,17 @@ _SIGS = [
     ("gbpe_bpe_free", None, [C.c_void_p]),
     ("gbpe_encode_last_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                           C.POINTER(C.c_double)]),
+    ("gbpe_vocab_upload", C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("gbpe_vocab_free", None, [C.c_void_p]),
+    ("gbpe_decode_size", C.c_int, [u64p, C.c_uint32, u32p, C.c_uint64, u64p]),
+    ("gbpe_decode", C.c_int, [C.c_void_p, C.c_void_p, u32p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]),
+    ("gbpe_decode_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]),
+    ("gbpe_decode_batch", C.c_int, [C.c_void_p, C.c_void_p, u32p, C.c_uint64, u64p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                    u64p, u64p]),
+    ("gbpe_decode_batch_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                           C.c_void_p, C.c_uint64, C.c_void_p, u64p]),
+    ("gbpe_decode_last_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                          C.POINTER(C.c_double)]),
     ("gbpe_device_alloc", C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
     ("gbpe_device_free", C.c_int, [C.c_void_p, C.c_void_p]),
     ("gbpe_memcpy_h2d", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),

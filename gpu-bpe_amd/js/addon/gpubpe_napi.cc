@@ -17,6 +17,9 @@
 //   trieUpload(ctx, nodes: Uint32Array, edges: Uint32Array) -> trie      trieFree(trie)
 //   encode(ctx, trie, bytes, chunkSize) -> Promise<Uint32Array>
 //   encodeBatch(ctx, trie, bytes, offsets: Float64Array, chunkSize) -> Promise<{tokens: Uint32Array, offsets: Float64Array}>
+//   vocabUpload(ctx, bytes: Uint8Array, offsets: Float64Array) -> vocab   vocabFree(vocab)
+//   decode(ctx, vocab, tokens: Uint32Array) -> Promise<Uint8Array>
+//   decodeBatch(ctx, vocab, tokens: Uint32Array, offsets: Float64Array) -> Promise<{bytes: Uint8Array, offsets: Float64Array}>
 //   wordBoundary(ctx, bytes) -> Uint8Array
 //
 // Concurrency and lifetimes.  Every call that touches a context's device state
@@ -24,10 +27,10 @@
 // so overlapping Promises (Promise.all over encode / trainerStep) run one after
 // the other on the device instead of racing (the reference serialises them on
 // one WebGPU queue).  Contexts are reference-counted by their trainers, tries,
-// BPE tables and in-flight work: destroyContext() closes a context for new
+// BPE tables, device vocabs and in-flight work: destroyContext() closes a context for new
 // calls, and the device context is freed when the last of those is gone.
-// trainerDestroy() / trieFree() during a step / encode defer the free to its
-// completion.
+// trainerDestroy() / trieFree() / vocabFree() during a step / encode / decode
+// defer the free to its completion.
 #include <node_api.h>
 
 #include <cstdint>
@@ -733,6 +736,205 @@ napi_value EncodeBatch(napi_env env, napi_callback_info info) {
     return promise;
 }
 
+// ── device vocab + decode (gbpe_vocab_upload, gbpe_decode, gbpe_decode_batch; an
+//    addition to the reference's API, whose decode is a host loop) ────────────
+struct DVocab {
+    gbpe_vocab* vocab = nullptr;
+    Ctx* owner = nullptr;
+    std::vector<uint64_t> offsets;   // host copy: gbpe_decode_size sizes every output exactly
+    int inflight = 0;
+    bool destroy_pending = false;
+};
+void dvocab_free(DVocab* v) {
+    if (v->vocab) {
+        std::lock_guard<std::mutex> g(v->owner->mu);
+        gbpe_vocab_free(v->vocab);
+        v->vocab = nullptr;
+    }
+    if (v->owner) {
+        ctx_release(v->owner);
+        v->owner = nullptr;
+    }
+}
+void dvocab_finalize(napi_env, void* data, void*) {
+    DVocab* v = static_cast<DVocab*>(data);
+    dvocab_free(v);
+    delete v;
+}
+
+// offsets cross the boundary as Float64Array (exact below 2^53); false: not one, or not non-negative integers
+bool get_offsets(napi_env env, napi_value v, std::vector<uint64_t>* out) {
+    bool is_ta = false;
+    napi_is_typedarray(env, v, &is_ta);
+    if (!is_ta) return false;
+    napi_typedarray_type type;
+    size_t length = 0, offset = 0;
+    void* raw = nullptr;
+    napi_value ab;
+    if (napi_get_typedarray_info(env, v, &type, &length, &raw, &ab, &offset) != napi_ok) return false;
+    if (type != napi_float64_array || length < 1) return false;
+    const double* offs = static_cast<const double*>(raw);
+    out->resize(length);
+    for (size_t i = 0; i < length; ++i) {
+        if (!(offs[i] >= 0 && offs[i] <= 9007199254740992.0) || offs[i] != (double)(uint64_t)offs[i]) return false;
+        (*out)[i] = (uint64_t)offs[i];
+    }
+    return true;
+}
+
+napi_value VocabUpload(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Ctx* c = argc >= 1 ? unwrap_external<Ctx>(env, argv[0]) : nullptr;
+    const uint8_t* bytes = nullptr;
+    size_t nb = 0;
+    auto* v = new DVocab();
+    if (!ctx_usable(c) || argc < 3 || !get_bytes(env, argv[1], &bytes, &nb) || !get_offsets(env, argv[2], &v->offsets) ||
+        v->offsets.size() - 1 > 0xFFFFFFFEull || v->offsets.back() > nb) {
+        delete v;
+        napi_throw_type_error(env, nullptr, "vocabUpload(ctx, bytes: Uint8Array, offsets: Float64Array of V + 1 entries within bytes)");
+        return nullptr;
+    }
+    std::unique_lock<std::mutex> g(c->mu);
+    const int rc = gbpe_vocab_upload(c->ctx, bytes, v->offsets.data(), (uint32_t)(v->offsets.size() - 1), &v->vocab);
+    g.unlock();
+    if (rc != GBPE_OK) {
+        delete v;
+        return throw_status(env, c->ctx, "vocab upload", rc);
+    }
+    v->owner = c;
+    ++c->refs;
+    napi_value ext;
+    NAPI_CALL(env, napi_create_external(env, v, dvocab_finalize, nullptr, &ext));
+    return ext;
+}
+
+napi_value VocabFree(napi_env env, napi_callback_info info) {
+    size_t argc = 1;
+    napi_value argv[1];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    DVocab* v = argc ? unwrap_external<DVocab>(env, argv[0]) : nullptr;
+    if (v && v->vocab) {
+        if (v->inflight) v->destroy_pending = true;   // decode_complete frees it
+        else dvocab_free(v);
+    }
+    return nullptr;
+}
+
+struct DecodeWork {   // decode and decodeBatch (batch: tok_off has D + 1 entries)
+    napi_async_work work = nullptr;
+    napi_deferred deferred = nullptr;
+    napi_ref keep_in = nullptr, keep_ctx = nullptr, keep_vocab = nullptr;
+    Ctx* c = nullptr;
+    DVocab* vocab = nullptr;
+    const uint32_t* tokens = nullptr;
+    size_t n = 0;
+    bool batch = false;
+    std::vector<uint64_t> tok_off, byte_off;   // (the offsets are copied on the JS thread)
+    std::vector<uint8_t> out;
+    uint64_t n_out = 0;
+    int rc = GBPE_OK;
+    std::string err;
+};
+
+void decode_execute(napi_env, void* data) {
+    auto* w = static_cast<DecodeWork*>(data);
+    uint64_t size = 0;
+    w->rc = gbpe_decode_size(w->vocab->offsets.data(), (uint32_t)(w->vocab->offsets.size() - 1), w->tokens, w->n, &size);
+    if (w->rc != GBPE_OK) {
+        w->err = last_error(nullptr, "decode size", w->rc);
+        return;
+    }
+    w->out.resize(size ? size : 1);
+    std::lock_guard<std::mutex> g(w->c->mu);
+    if (w->batch) {
+        w->byte_off.assign(w->tok_off.size(), 0);
+        w->rc = gbpe_decode_batch(w->c->ctx, w->vocab->vocab, w->tokens, w->n, w->tok_off.data(), w->tok_off.size() - 1,
+                                  w->out.data(), size, w->byte_off.data(), &w->n_out);
+    } else {
+        w->rc = gbpe_decode(w->c->ctx, w->vocab->vocab, w->tokens, w->n, w->out.data(), size, &w->n_out);
+    }
+    if (w->rc != GBPE_OK) w->err = last_error(w->c->ctx, w->batch ? "decode batch" : "decode", w->rc);
+}
+
+napi_value make_u8_array(napi_env env, const uint8_t* src, size_t n) {
+    napi_value ab, ta;
+    void* dst = nullptr;
+    if (napi_create_arraybuffer(env, n, &dst, &ab) != napi_ok) return nullptr;
+    if (n) memcpy(dst, src, n);
+    if (napi_create_typedarray(env, napi_uint8_array, n, ab, 0, &ta) != napi_ok) return nullptr;
+    return ta;
+}
+
+void decode_complete(napi_env env, napi_status, void* data) {
+    auto* w = static_cast<DecodeWork*>(data);
+    if (w->rc != GBPE_OK) {
+        napi_value msg, err;
+        napi_create_string_utf8(env, w->err.c_str(), NAPI_AUTO_LENGTH, &msg);
+        napi_create_error(env, nullptr, msg, &err);
+        napi_reject_deferred(env, w->deferred, err);
+    } else if (!w->batch) {
+        napi_resolve_deferred(env, w->deferred, make_u8_array(env, w->out.data(), (size_t)w->n_out));
+    } else {
+        napi_value obj, ab, offs;
+        void* dst = nullptr;
+        napi_create_object(env, &obj);
+        napi_set_named_property(env, obj, "bytes", make_u8_array(env, w->out.data(), (size_t)w->n_out));
+        const size_t no = w->byte_off.size();
+        napi_create_arraybuffer(env, no * 8, &dst, &ab);
+        for (size_t i = 0; i < no; ++i) static_cast<double*>(dst)[i] = (double)w->byte_off[i];
+        napi_create_typedarray(env, napi_float64_array, no, ab, 0, &offs);
+        napi_set_named_property(env, obj, "offsets", offs);
+        napi_resolve_deferred(env, w->deferred, obj);
+    }
+    if (--w->vocab->inflight == 0 && w->vocab->destroy_pending) dvocab_free(w->vocab);
+    ctx_release(w->c);
+    napi_delete_reference(env, w->keep_in);
+    napi_delete_reference(env, w->keep_ctx);
+    napi_delete_reference(env, w->keep_vocab);
+    napi_delete_async_work(env, w->work);
+    delete w;
+}
+
+napi_value decode_queue(napi_env env, napi_callback_info info, bool batch) {
+    size_t argc = 4;
+    napi_value argv[4];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Ctx* c = argc >= 1 ? unwrap_external<Ctx>(env, argv[0]) : nullptr;
+    DVocab* v = argc >= 2 ? unwrap_external<DVocab>(env, argv[1]) : nullptr;
+    const uint32_t* tokens = nullptr;
+    size_t n = 0;
+    std::vector<uint64_t> tok_off;
+    if (!ctx_usable(c) || !v || !v->vocab || v->destroy_pending || argc < (batch ? 4u : 3u) ||
+        !get_u32s(env, argv[2], &tokens, &n) || (batch && !get_offsets(env, argv[3], &tok_off))) {
+        napi_throw_type_error(env, nullptr, batch ? "decodeBatch(ctx, vocab, Uint32Array, offsets: Float64Array of non-negative integers)"
+                                                  : "decode(ctx, vocab, Uint32Array)");
+        return nullptr;
+    }
+    auto* w = new DecodeWork();
+    w->c = c;
+    ++c->refs;        // released by decode_complete
+    w->vocab = v;
+    ++v->inflight;
+    w->tokens = tokens;
+    w->n = n;
+    w->batch = batch;
+    w->tok_off = std::move(tok_off);
+    napi_value promise, name;
+    NAPI_CALL(env, napi_create_promise(env, &w->deferred, &promise));
+    NAPI_CALL(env, napi_create_reference(env, argv[2], 1, &w->keep_in));
+    NAPI_CALL(env, napi_create_reference(env, argv[0], 1, &w->keep_ctx));
+    NAPI_CALL(env, napi_create_reference(env, argv[1], 1, &w->keep_vocab));
+    NAPI_CALL(env, napi_create_string_utf8(env, batch ? "gpubpe.decodeBatch" : "gpubpe.decode", NAPI_AUTO_LENGTH, &name));
+    NAPI_CALL(env, napi_create_async_work(env, nullptr, name, decode_execute, decode_complete, w, &w->work));
+    NAPI_CALL(env, napi_queue_async_work(env, w->work));
+    return promise;
+}
+
+napi_value Decode(napi_env env, napi_callback_info info) { return decode_queue(env, info, false); }
+napi_value DecodeBatch(napi_env env, napi_callback_info info) { return decode_queue(env, info, true); }
+
 napi_value Init(napi_env env, napi_value exports) {
     napi_property_descriptor props[] = {
         {"createContext", nullptr, CreateContext, nullptr, nullptr, nullptr, napi_default, nullptr},
@@ -750,6 +952,10 @@ napi_value Init(napi_env env, napi_value exports) {
         {"trieFree", nullptr, TrieFree, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"encode", nullptr, Encode, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"encodeBatch", nullptr, EncodeBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"vocabUpload", nullptr, VocabUpload, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"vocabFree", nullptr, VocabFree, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"decode", nullptr, Decode, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"decodeBatch", nullptr, DecodeBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
     };
     napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
     return exports;

@@ -73,7 +73,46 @@ export class TrieTokenizer {
         return out;
     }
 
+    /** The vocab table on the device, uploaded on first use. */
+    _deviceVocab() {
+        if (!this._dvocab) {
+            const offsets = new Float64Array(this._vocab.length + 1);
+            for (let i = 0; i < this._vocab.length; i++) offsets[i + 1] = offsets[i] + this._vocab[i].length;
+            const bytes = new Uint8Array(offsets[this._vocab.length]);
+            for (let i = 0; i < this._vocab.length; i++) bytes.set(this._vocab[i], offsets[i]);
+            this._dvocab = native().vocabUpload(this._engine.device, bytes, offsets);
+        }
+        return this._dvocab;
+    }
+
+    /** decode() on the device (an addition to the reference's API): the same bytes. */
+    async decodeBytes(tokens) {
+        if (tokens.length === 0) return new Uint8Array(0);
+        const t = tokens instanceof Uint32Array ? tokens : Uint32Array.from(tokens);
+        return native().decode(this._engine.device, this._deviceVocab(), t);
+    }
+
+    /**
+     * Many token documents in one device call: one Uint8Array per document,
+     * each what decode returns for that document alone, all views into one
+     * shared buffer (mirrors encodeBatch).
+     */
+    async decodeBatch(docs) {
+        const offsets = new Float64Array(docs.length + 1);
+        for (let d = 0; d < docs.length; d++) offsets[d + 1] = offsets[d] + docs[d].length;
+        const total = offsets[docs.length];
+        if (docs.length === 0 || total === 0) return docs.map(function () { return new Uint8Array(0); });
+        const tokens = new Uint32Array(total);
+        for (let d = 0; d < docs.length; d++) tokens.set(docs[d], offsets[d]);
+        const r = await native().decodeBatch(this._engine.device, this._deviceVocab(), tokens, offsets);
+        const views = [];
+        for (let d = 0; d < docs.length; d++) views.push(r.bytes.subarray(r.offsets[d], r.offsets[d + 1]));
+        return views;
+    }
+
     destroy() {
+        if (this._dvocab) native().vocabFree(this._dvocab);
+        this._dvocab = null;
         if (this._trie) native().trieFree(this._trie);
         this._trie = null;
     }

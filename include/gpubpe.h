@@ -28,7 +28,8 @@
 extern "C" {
 #endif
 
-#define GBPE_ABI_VERSION 7   /* 7: gbpe_encode_batch, gbpe_encode_batch_device (many documents in one call);
+#define GBPE_ABI_VERSION 8   /* 8: device decode (gbpe_vocab_upload, gbpe_decode*, gbpe_decode_batch*);
+                                 7: gbpe_encode_batch, gbpe_encode_batch_device (many documents in one call);
                                  6: pair_candidates, pair_rejected added at the end of the stats; 5: paired_merges
                                  added to the stats, gbpe_ctx_trim (round 6); 4: the late-loop stats removed,
                                  trainer creation time added (round 5) */
@@ -53,6 +54,7 @@ extern "C" {
 typedef struct gbpe_ctx gbpe_ctx;
 typedef struct gbpe_trainer gbpe_trainer;
 typedef struct gbpe_trie gbpe_trie;
+typedef struct gbpe_vocab gbpe_vocab;
 
 /* ── context / device (replaces engine.js:143-177 requestGPUDevice and
  *    engine.js:216-238 BPEEngine.init) ─────────────────────────────────── */
@@ -365,6 +367,71 @@ void gbpe_bpe_free(gbpe_bpe* bpe);
  * the compaction with the document token offsets (the last group's, when the host
  * variant ran several) */
 int gbpe_encode_last_timing(gbpe_ctx* ctx, double* ms_walk, double* ms_scan, double* ms_compact);
+
+/* ── device decode (replaces the host loop of tokenizer.js:344-363 decode) ───
+ * Token ids back to bytes: per-token lengths, an exclusive scan, a scatter of
+ * the vocab bytes.  The output is exactly the reference's decode:
+ * each id's vocab bytes in order, and every id >= the vocab's n_tokens —
+ * 0xFFFFFFFF included — yields EF BF BD (U+FFFD, tokenizer.js:18, 350).  Such an
+ * id is clamped before any table read, so a bad id never becomes an
+ * out-of-range load. */
+
+/* Token id i has bytes[offsets[i] .. offsets[i+1]) — the layout gbpe_trie_compile
+   takes.  Empty entries are allowed and decode to nothing.  An entry longer than
+   65,535 bytes is GBPE_E_INVALID (a 4096-token block's byte prefix then fits 32
+   bits), and so are offsets that decrease. */
+int  gbpe_vocab_upload(gbpe_ctx* ctx, const uint8_t* bytes, const uint64_t* offsets, uint32_t n_tokens,
+                       gbpe_vocab** out);
+void gbpe_vocab_free(gbpe_vocab* vocab);
+
+/* Host only (no context, no device), like gbpe_trie_compile: the exact decoded
+   size.  An id >= n_vocab counts 3 bytes (U+FFFD, tokenizer.js:18, 350).
+   tokens may be NULL when n_tokens == 0; any other null argument is GBPE_E_INVALID. */
+int  gbpe_decode_size(const uint64_t* vocab_offsets, uint32_t n_vocab, const uint32_t* tokens, uint64_t n_tokens,
+                      uint64_t* n_bytes);
+
+/* Host buffers in and out.  n_tokens == 0: GBPE_OK, *n_out = 0, nothing launched.
+ * On GBPE_E_CAPACITY *n_out holds the required byte count, the first out_cap
+ * bytes are in out and nothing is written at or beyond out[out_cap].  Token
+ * streams above the decode slice (32M tokens) run slice by slice through the
+ * context's pooled buffers; a slice may start at any token. */
+int gbpe_decode(gbpe_ctx* ctx, gbpe_vocab* vocab, const uint32_t* tokens, uint64_t n_tokens, uint8_t* out,
+                uint64_t out_cap, uint64_t* n_out);
+/* Device-resident variant: d_tokens (u32, 4-byte aligned) and d_out (16-byte
+ * aligned) are device pointers; a wrong alignment is GBPE_E_INVALID with
+ * *n_out = 0 and nothing launched.  Only d_tokens[0, n_tokens) is read and only
+ * d_out[0, min(total, out_cap)) is ever written; on GBPE_E_CAPACITY *n_out holds
+ * the required byte count and the first out_cap bytes are in d_out. */
+int gbpe_decode_device(gbpe_ctx* ctx, gbpe_vocab* vocab, const void* d_tokens, uint64_t n_tokens, void* d_out,
+                       uint64_t out_cap, uint64_t* n_out);
+/* Many documents in one call: the documents' tokens lie end to end in `tokens`;
+ * tok_off has n_docs + 1 non-decreasing entries, tok_off[0] == 0 and
+ * tok_off[n_docs] == n_tokens, and document d is tokens[tok_off[d] .. tok_off[d+1])
+ * (empty documents allowed).  out receives every document's bytes in order — the
+ * bytes gbpe_decode gives the whole stream — and byte_off (n_docs + 1 entries)
+ * their boundaries: out[byte_off[d] .. byte_off[d+1]) is document d.  On
+ * GBPE_E_CAPACITY *n_out holds the required byte count, byte_off is complete, the
+ * first out_cap bytes are in place and nothing is written at or beyond
+ * out[out_cap].  n_docs == 0 or n_tokens == 0: GBPE_OK, *n_out = 0, every byte_off
+ * entry 0.  Bad offsets: GBPE_E_INVALID (checked on the host before anything is
+ * launched).  Above the decode slice a document may span slices: a byte_off entry
+ * comes from the slice that holds token tok_off[d], shifted by the running total. */
+int gbpe_decode_batch(gbpe_ctx* ctx, gbpe_vocab* vocab, const uint32_t* tokens, uint64_t n_tokens,
+                      const uint64_t* tok_off, uint64_t n_docs, uint8_t* out, uint64_t out_cap, uint64_t* byte_off,
+                      uint64_t* n_out);
+/* Device-resident variant: d_tokens (4-byte aligned), d_tok_off and d_byte_off
+ * (u64, 8-byte aligned) and d_out (16-byte aligned) are device pointers.  The
+ * offsets are checked on the device by the kernel that writes d_byte_off, which
+ * never indexes the prefix arrays with an entry above n_tokens; the status comes
+ * back with the total, and on bad offsets (GBPE_E_INVALID, *n_out = 0) the scatter
+ * is not launched, d_out is untouched and d_byte_off is unspecified. */
+int gbpe_decode_batch_device(gbpe_ctx* ctx, gbpe_vocab* vocab, const void* d_tokens, uint64_t n_tokens,
+                             const void* d_tok_off, uint64_t n_docs, void* d_out, uint64_t out_cap, void* d_byte_off,
+                             uint64_t* n_out);
+/* device ms of the last decode's kernels: lengths + block scan, the scan of the
+ * block sums with the document byte offsets, the scatter (the last slice's, when
+ * the host variant ran several) */
+int gbpe_decode_last_timing(gbpe_ctx* ctx, double* ms_len, double* ms_scan, double* ms_scatter);
 
 /* ── device memory helpers for device-resident callers ─────────────────── */
 int gbpe_device_alloc(gbpe_ctx* ctx, uint64_t bytes, void** dptr);
