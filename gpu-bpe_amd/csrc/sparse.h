@@ -762,8 +762,9 @@ struct SelShard {
     uint32_t zf = SP_ZONE_F; // zone rule: z >= max(2 mc + mc_prev, zf mc) + 2
     uint32_t sub = 1;        // k_body workgroups per bitmap word (1, 2, 4: a row of few words, body_grid)
     uint32_t k2 = 0;         // paired launches allowed (the zone_one form: zone_two)
-    uint32_t prej = 0;       // tests (GBPE_DEBUG prej): zone_two's verdict also rejects candidate c when
-                             // c % prej == prej - 1 (0: off; reference compaction only)
+    uint32_t prej = 0;       // tests (GBPE_DEBUG prej): the paired launch's verdict also rejects candidate c
+                             // when c % prej == prej - 1 (0: off; reference compaction only)
+    uint32_t churn = 0;      // block 1 is the paired launch's churn workgroup (pair_churn; reference compaction)
 };
 
 // The second merge of a paired launch.  With P1 > P2 the table's two
@@ -916,6 +917,182 @@ __device__ __forceinline__ bool sel_inline(DevState* st, DevState* zst, const ui
 // epoch << 2 | 2 (decided) | 1 (accepted)
 __device__ __forceinline__ uint32_t* pair_word(ZSegState* zg) { return &zg->pad[1]; }
 
+// Churn workgroup of a paired launch under the reference compaction (block 1 of
+// k_body): merge 1's two mc-long chores — the stale tail's destroyed
+// pairs and the stale window's new ones — and the verdict, beside the zone
+// workgroup's pass instead of inside its chain.  Its inputs are local: the zone's
+// last mc + 2 symbols, the mc window-source symbols of the other buffer, P2 and the
+// table counts of the window's pairs.  It waits on nobody; the zone workgroup and
+// the body workgroups wait on its verdict word.
+//  * Merge 1's hits inside [lim - 1, z) need the symbols from lim - 2 on: they give
+//    m (the tail's survivors = the window's length) and the state of position
+//    lim - 1, the window's left neighbour when it is kept.  When it is not kept the
+//    last kept survivor is the A-side before a run of B-sides, which reads nw; so
+//    does a kept lim - 1 that position lim rewrites.  Either rejects.
+//  * Verdict with churn-only deltas: this table holds merge 1's tail and window
+//    deltas but not its site deltas.  A pair without nw only ever gets decrements
+//    from sites, in the zone and in the body alike, so the churn-only delta bounds
+//    the net delta from above, and so does the count read now.  P2 is token-disjoint
+//    from P1: no site delta touches it, and its churn delta is its net delta.  This
+//    table's overflow rejects.  Over-rejection only costs speed.
+//  * No workgroup sends a merge-2 delta to the global table before the verdict is
+//    published (the zone and the body workgroups start merge 2 after they saw the
+//    word; this one runs no merge 2), which keeps "the count read is an upper
+//    bound" true.
+//  * Every read of the zone buffers here is done before the word is stored, and the
+//    zone workgroup stores to neither buffer before it saw the word.
+template <typename S, int BT, int NT>
+__device__ __forceinline__ void pair_churn(DevState* st, const DevState& gs, uint32_t z, const S* __restrict__ zc,
+                                           const S* __restrict__ zo, ZSegState* zg, ZoneLds<S, BT>& L, LdsTab<NT>& ltab,
+                                           const Table& tb, uint32_t a, uint32_t b, uint32_t nw, uint32_t mc,
+                                           const Sel2& s2, uint64_t* __restrict__ bytes, uint32_t round, uint32_t prej) {
+    (void)round;   // phase stamps only (-DGBPE_KTRACE: 2 loaded, 3 adds done, 8 verdict; the caller stamps 5)
+    constexpr uint32_t WS = Sym<S>::WS, TM = Sym<S>::TM;
+    constexpr int KV = (ZoneDim<S, BT>::ZWIN + BT - 1) / BT;   // tail / window pairs per thread (m <= mc <= ZWIN)
+    __shared__ uint32_t s_crej, s_cm[BT / 64];
+    const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+    const uint32_t mc2 = s2.mc, pid1 = (a << 16) | b, pid2 = (s2.a << 16) | s2.b;
+    const uint32_t lim = z - mc;   // >= 2 mc + 2 (sel_inline's zone rule)
+    // the tail and the window are <= 2 mc pairs: a table at <= ~1/2 load
+    uint32_t nslot = 1024u;
+    while (nslot < (uint32_t)NT && nslot < 4u * mc) nslot <<= 1;
+    LdsView lt = lds_view(ltab, nslot);
+    lds_clear(lt);
+    if (t == 0) s_crej = 0u;
+    // P2's home slot for its commit, loaded with the symbols
+    const uint32_t h2i = gbpe_fmix32(pid2) & tb.mask;
+    uint64_t h2 = 0;
+    if (t == 0)
+        h2 = __hip_atomic_load(reinterpret_cast<const uint64_t*>(&tb.slots[h2i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    S* xs = reinterpret_cast<S*>(L.xv);   // xs[i] = zone position lim - 2 + i, i in [0, mc + 2)
+    {   // both ranges in one round trip (8 loads in flight per thread)
+        const S* tsrc = zc + (lim - 2u);
+        const S* wsrc = zo + win_src0(gs, mc);
+        for (uint32_t i0 = t; i0 < mc + 2u; i0 += 4u * BT) {
+            S v[4], w[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const uint32_t i = i0 + (uint32_t)u * BT;
+                v[u] = i < mc + 2u ? tsrc[i] : (S)0;
+                w[u] = i < mc ? wsrc[i] : (S)0;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const uint32_t i = i0 + (uint32_t)u * BT;
+                if (i < mc + 2u) xs[i] = v[u];
+                if (i < mc) L.wb[i] = w[u];
+            }
+        }
+    }
+    __syncthreads();
+    if (t == 0) KT(2);
+    KTC(0);
+    // the stale tail [lim, z): merge 1's hits (a survivor is any other position) and the old pairs destroyed
+    uint32_t tq[KV], surv = 0;
+#pragma unroll
+    for (int k = 0; k < KV; ++k) {
+        tq[k] = 0u;
+        if ((uint32_t)k * BT >= mc) continue;   // (workgroup-uniform: a late merge fills a few of the KV rounds)
+        // (reads at a clamped index, outside the branch: every round's LDS reads issue together)
+        const uint32_t i = 2u + (uint32_t)t + (uint32_t)k * BT, ic = i < mc + 2u ? i : mc + 1u;
+        const uint32_t xi = xs[ic], xp = xs[ic - 1], tp = xp & TM, ti = xi & TM;
+        if (i < mc + 2u) {
+            surv += (xi == b && tp == a) ? 0u : 1u;
+            if (!(xi & WS) && tp && ti && ((tp << 16) | ti) != pid1) tq[k] = (tp << 16) | ti;
+        }
+    }
+    surv = wave_sum_u32(surv);
+    if (lane == 0) s_cm[wid] = surv;
+    __syncthreads();   // (m first: the window pairs' count loads are issued before any add and arrive during them)
+    uint32_t m = 0;
+#pragma unroll
+    for (int w2 = 0; w2 < BT / 64; ++w2) m += s_cm[w2];
+    // position lim - 1: kept unless it is a B-side; rewritten when position lim is its B-side
+    const uint32_t xl1 = xs[1];
+    const bool kept1 = !(xl1 == b && ((uint32_t)xs[0] & TM) == a), rew1 = (uint32_t)xs[2] == b && (xl1 & TM) == a;
+    const uint32_t left0 = (kept1 && !rew1) ? (xl1 & TM) : nw;   // the last kept survivor's token
+    if (t == 0 && m && (!kept1 || rew1)) s_crej = 1u;
+    // the window = source [mc - m, mc): its pairs, and their counts' loads (plain loads: a line older than
+    // the body workgroups' adds to a pair holds a count at least its final one, those adds being decrements)
+    const uint32_t woff = mc - m;
+    uint32_t wq[KV], vq[KV];
+    uint64_t vh[KV];
+#pragma unroll
+    for (int k = 0; k < KV; ++k) {
+        wq[k] = 0u;
+        vq[k] = 0u;
+        vh[k] = 0;
+        if ((uint32_t)k * BT >= m) continue;   // (workgroup-uniform; m > 0 below)
+        const uint32_t j = (uint32_t)t + (uint32_t)k * BT, jc = j < m ? j : 0u;
+        const uint32_t x1 = L.wb[woff + jc], xw = L.wb[woff + (jc ? jc - 1u : 0u)];
+        if (j < m) {
+            const uint32_t xl = j ? xw & TM : left0;
+            if (!(x1 & WS) && xl && (x1 & TM)) {
+                const uint32_t q = (xl << 16) | (x1 & TM);
+                wq[k] = q;
+                if (xl == nw) s_crej = 1u;   // a pair of the new token that no site made
+                else vq[k] = q;
+            }
+            // (P1's count is 0 after its commit; P2: its delta alone decides)
+            if (vq[k] && vq[k] != pid1 && vq[k] != pid2)
+                vh[k] = reinterpret_cast<const uint64_t*>(tb.slots)[gbpe_fmix32(vq[k]) & tb.mask];
+        }
+    }
+    KTC(1);
+    lds_addk<KV>(lt, tb, st, tq, 0xFFFFFFFFu);
+    lds_addk<KV>(lt, tb, st, wq, 1u);
+    KTC(2);
+    __syncthreads();
+    if (t == 0) KT(3);
+    // ── the verdict ──
+    bool rej = false;
+    if (t == 0) rej = s_crej != 0u || *lt.ovf != 0u || lds_find(lt, pid2) != 0u;
+#pragma unroll
+    for (int k = 0; k < KV; ++k) {
+        if (!vq[k] || vq[k] == pid2) continue;
+        const uint32_t d = lds_find(lt, vq[k]);
+        if ((int32_t)d <= 0) continue;
+        uint32_t cnt = 0;
+        if (vq[k] != pid1) {
+            if ((uint32_t)vh[k] == vq[k]) {
+                cnt = (uint32_t)(vh[k] >> 32);
+            } else {
+                const uint32_t idx = table_find(tb, vq[k]);
+                cnt = idx == 0xFFFFFFFFu ? 0u : __hip_atomic_load(&tb.slots[idx].y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            if ((int32_t)cnt < 0) cnt = 0;
+        }
+        const uint64_t c2 = (uint64_t)cnt + d;
+        if (c2 > mc2 || (c2 == mc2 && vq[k] < pid2)) rej = true;
+    }
+    // tests (GBPE_DEBUG prej): every prej-th candidate is turned down after the verdict above ran
+    // (gs: the launch's snapshot of the state; only this workgroup counts candidates)
+    if (t == 0 && prej && gs.pair_cand % prej == prej - 1u) rej = true;
+    rej = __syncthreads_or(rej) != 0;
+    KTC(3);
+    if (t == 0) {
+        st->pair_cand += 1u;   // (the stats' pair_candidates / pair_rejected: one churn workgroup per launch)
+        if (rej) st->pair_rej += 1u;
+        if (!rej) {   // commit P2: every occurrence is a site of the second merge
+            const uint32_t idx = (uint32_t)h2 == pid2 ? h2i : table_find(tb, pid2);
+            if (idx == 0xFFFFFFFFu) {
+                atomicOr(&st->err, ERR_PAIR_MISSING);
+            } else {
+                atomicSub(&tb.slots[idx].y, mc2);
+                tb.dirty[idx >> BLK_LOG2] = 1u;
+            }
+            st->acc2 = 1u;
+        }
+        __hip_atomic_store(pair_word(zg), (gs.epoch << 2) | (rej ? 2u : 3u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        KT(8);
+    }
+    lds_flush<NT / BT>(lt, tb, st);
+    if (t == 0) {
+        KT(4);
+        atomicAdd(bytes, (uint64_t)sizeof(S) * (2ull * mc + 2u));   // the tail and the window source read
+    }
+}
+
 // Zone workgroup of a paired launch: both merges in one pass over the
 // zone — one load, the first merge's zone assembled in LDS, the verdict, the second
 // merge on that LDS copy, one store of each zone buffer and one flush.
@@ -928,14 +1105,12 @@ __device__ __forceinline__ uint32_t* pair_word(ZSegState* zg) { return &zg->pad[
 //    symbols, [z - mc - 2 mc2, + mc2) of the loaded zone, are staged in wb2 with the
 //    rewrites applied before LDS is overwritten.
 //  * Ref-mode verdict: the first merge's stale window (and the tail it replaces) may
-//    lift a pair over P2 or change P2's count.  Every zone delta of merge 1 is in
-//    the table (an overflow rejects): P2's net delta must be 0, and every window
-//    pair with a positive net delta must stay below P2 with its count read now (the
-//    body workgroups' adds to a pair without nw are decrements, so the read bounds
-//    the final count from above).  Pairs of nw come from sites (bounded, Sel2)
-//    except the window's first pair, whose left symbol (the last kept survivor at
-//    lim - 1) is checked: nw or not kept there rejects.  The window pairs' counts
-//    are loaded before the first merge's assembly, so the round trip overlaps it.
+//    lift a pair over P2 or change P2's count.  The churn workgroup (pair_churn)
+//    adds those deltas and decides; this workgroup adds only merge 1's site deltas,
+//    copies the window into its LDS zone, and reads the verdict word once merge 1
+//    is assembled (first load issued before the assembly, then the body's poll).
+//    It sends no merge-2 delta to the global table and stores to neither zone
+//    buffer before it saw the word.
 //  * zo ends as the first merge's output with the second's A-side rewrites (a later
 //    window reads it), zc as the second's output.  Rejected: the first merge's
 //    output goes to zo and its rewrites to zc, as zone_one leaves them.
@@ -943,39 +1118,36 @@ template <typename S, bool EXACT, int BT, int NT, int ZPT>
 __device__ __forceinline__ void zone_two(DevState* st, DevState* zst, const DevState& gs, uint32_t z, S* __restrict__ zc,
                                          S* __restrict__ zo, ZSegState* zg, ZoneLds<S, BT>& L, S* __restrict__ wb2,
                                          LdsTab<NT>& ltab, const Table& tb, uint32_t a, uint32_t b, uint32_t nw,
-                                         uint32_t mc, const Sel2& s2, uint64_t* __restrict__ bytes, uint32_t round,
-                                         uint32_t prej) {
-    (void)round;   // phase stamps only (-DGBPE_KTRACE: 2 loaded, 3 merge-1 deltas, 7 merge 1 in LDS, 8 verdict,
-                   // 9 merge 2 in LDS, 4 stored; the caller stamps 5 after the flush)
+                                         uint32_t mc, const Sel2& s2, uint64_t* __restrict__ bytes, uint32_t round) {
+    (void)round;   // phase stamps only (-DGBPE_KTRACE: 2 loaded, 3 merge-1 deltas, 7 merge 1 in LDS, 8 verdict
+                   // seen, 9 merge 2 in LDS, 4 stored; the caller stamps 5 after the flush)
     constexpr uint32_t WS = Sym<S>::WS, TM = Sym<S>::TM;
     static_assert(ZPT == ZoneDim<S, BT>::ZPT && ZPT * sizeof(S) % 16 == 0, "zone positions per thread");
     constexpr int V = ZPT * sizeof(S) / 16;
     constexpr uint32_t PV = 16 / sizeof(S), PVL = sizeof(S) == 2 ? 3 : 2;
     constexpr uint32_t TG = ZPT * sizeof(S) >= 128 ? 1u : 128u / (ZPT * sizeof(S));   // threads per swizzle group
-    constexpr int KV = (ZoneDim<S, BT>::ZWIN + BT - 1) / BT;   // window pairs per thread (m <= mc <= ZWIN)
     auto swz = [](uint32_t o) -> uint32_t {   // 16-byte chunks XOR-swizzled in groups of 8 (zone_one)
         const uint32_t c = o >> PVL;
         return ((c ^ ((c >> 3) & 7u)) << PVL) | (o & (PV - 1u));
     };
-    __shared__ uint32_t s_rej, s_x0, s_tf1, s_tf2;
+    __shared__ uint32_t s_tf1, s_tf2;
     const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
     const uint32_t a2 = s2.a, b2 = s2.b, n2 = nw + 1u, mc2 = s2.mc;
     const uint32_t pid1 = (a << 16) | b, pid2 = (a2 << 16) | b2;
-    // both merges' tails and windows are <= 2 (mc + mc2) pairs: a table at <= ~1/2 load
+    // merge 2's tail and window are <= 2 mc2 pairs (merge 1's are the churn workgroup's; the sites' deltas
+    // are few): a table at <= ~1/2 load
     uint32_t nslot = 1024u;
-    while (nslot < (uint32_t)NT && nslot < 4u * (mc + mc2)) nslot <<= 1;
+    while (nslot < (uint32_t)NT && nslot < 4u * mc2) nslot <<= 1;
     LdsView lt = lds_view(ltab, nslot);
     lds_clear(lt);
     if (t == 0) {
-        s_rej = 0u;
-        s_x0 = 0u;
         s_tf1 = BT;
         s_tf2 = BT;
     }
-    // P2's home slot for its commit, loaded while merge 1 runs
+    // exact mode (no verdict: this workgroup commits P2): its home slot, loaded while merge 1 runs
     const uint32_t h2i = gbpe_fmix32(pid2) & tb.mask;
     uint64_t h2 = 0;
-    if (t == 0)
+    if (EXACT && t == 0)
         h2 = __hip_atomic_load(reinterpret_cast<const uint64_t*>(&tb.slots[h2i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint32_t i0 = (uint32_t)t * ZPT;
     S* xs = reinterpret_cast<S*>(L.xv);
@@ -1020,18 +1192,7 @@ __device__ __forceinline__ void zone_two(DevState* st, DevState* zst, const DevS
         uint32_t rel = ((uint32_t)hbits | (uint32_t)(hbits >> 1) | (uint32_t)(hbits >> 2)) & below & inb;
         if (t == 0) KT(10);
         KTW(1);
-        for (uint32_t ib = (lim > 1u ? lim : 1u) + t; ib < z; ib += 4u * BT) {   // stale tail: old pairs destroyed
-            uint32_t kq[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const uint32_t i = ib + (uint32_t)k * BT;
-                const uint32_t xi = i < z ? (uint32_t)xs[i] : WS, tp = i < z ? (uint32_t)xs[i - 1] & TM : 0u, ti = xi & TM;
-                kq[k] = (!(xi & WS) && tp && ti && ((tp << 16) | ti) != pid1) ? (tp << 16) | ti : 0u;
-            }
-            lds_addk<4>(lt, tb, st, kq, 0xFFFFFFFFu);
-        }
-        if (t == 0) KT(11);
-        KTW(2);
+        // (the stale tail [lim, z)'s destroyed pairs are the churn workgroup's)
         while (rel) {
             const int k = __ffs(rel) - 1;
             rel &= rel - 1;
@@ -1060,11 +1221,6 @@ __device__ __forceinline__ void zone_two(DevState* st, DevState* zst, const DevS
             for (uint32_t p = w2 + t; p < w2 + mc2; p += BT) {
                 const uint32_t xp = xs[p], xn = p + 1u < z ? (uint32_t)xs[p + 1u] : 0u;
                 wb2[p - w2] = (S)(((xp & TM) == a && xn == b) ? (nw | (xp & WS)) : xp);
-            }
-            if (lim >= 1u && lim - 1u >= i0 && lim - 1u < i0 + ZPT) {   // the window's left neighbour, if kept
-                const uint32_t k = lim - 1u - i0;
-                if ((keep >> k) & 1u)
-                    s_x0 = 0x80000000u | (((rwm >> k) & 1u) ? (nw | (x[k] & WS)) : x[k]);
             }
         }
         KTW(4);
@@ -1095,34 +1251,10 @@ __device__ __forceinline__ void zone_two(DevState* st, DevState* zst, const DevS
     auto at1 = [&](uint32_t p) -> uint32_t {   // the first merge's zone in LDS (position p < z1)
         return p < F1 ? (uint32_t)xs[p] : (uint32_t)xs[swz(p)];
     };
-    // the verdict's window pairs: their counts load now and arrive during the assembly
     const uint32_t woff = mc - m;
-    uint32_t vq[KV];
-    uint64_t vh[KV];
-    if (!EXACT) {
-        const uint32_t x0 = s_x0;
-        if (t == 0 && m && Kz && !(x0 >> 31)) s_rej = 1u;   // the last kept survivor is not at lim - 1
-#pragma unroll
-        for (int k = 0; k < KV; ++k) {
-            const uint32_t j = (uint32_t)t + (uint32_t)k * BT;
-            vq[k] = 0u;
-            vh[k] = 0;
-            if (j < m) {
-                const uint32_t x1 = L.wb[woff + j];
-                const uint32_t xl = j ? (uint32_t)L.wb[woff + j - 1] : (Kz ? (x0 & 0x7FFFFFFFu) : 0u);
-                if (!(x1 & WS) && (xl & TM) && (x1 & TM)) {
-                    const uint32_t q = ((xl & TM) << 16) | (x1 & TM);
-                    if ((q >> 16) == nw) s_rej = 1u;   // a pair of the new token that no site made
-                    else vq[k] = q;
-                }
-                // (P1's count is 0 after its commit; P2: its net delta.)  Plain loads, not waited for
-                // here: a line older than the body workgroups' adds to this pair holds a count at
-                // least its final one (those adds are decrements), which only makes the check stricter
-                if (vq[k] && vq[k] != pid1 && vq[k] != pid2)
-                    vh[k] = reinterpret_cast<const uint64_t*>(tb.slots)[gbpe_fmix32(vq[k]) & tb.mask];
-            }
-        }
-    }
+    // ref mode: the verdict word's first load, issued now, arrives during the assembly
+    uint32_t pv = 0;
+    if (!EXACT && t == 0) pv = __hip_atomic_load(pair_word(zg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     KTW(6);
     // the first merge's zone in LDS past the unmoved prefix (every read of the old copy is done)
     if ((uint32_t)t >= tf1) {   // (8-symbol chunks no lane of the wave keeps are skipped: the stale tail)
@@ -1142,67 +1274,44 @@ __device__ __forceinline__ void zone_two(DevState* st, DevState* zst, const DevS
     if (!EXACT && m) {
         __syncthreads();
         KTW(8);
-        for (uint32_t jb = t; jb < m; jb += 4u * BT) {
-            uint32_t kq[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const uint32_t j = jb + (uint32_t)k * BT;
-                kq[k] = 0u;
-                if (j < m) {
-                    const uint32_t x1 = L.wb[woff + j];
-                    const uint32_t x0 = j ? (uint32_t)L.wb[woff + j - 1] : (Kz ? at1(Kz - 1) : 0u);
-                    xs[swz(Kz + j)] = (S)x1;
-                    if (!(x1 & WS) && (x0 & TM) && (x1 & TM)) kq[k] = ((x0 & TM) << 16) | (x1 & TM);
-                }
-            }
-            lds_addk<4>(lt, tb, st, kq, 1u);
-        }
+        // the window behind the kept survivors (its pairs are the churn workgroup's)
+        for (uint32_t j = t; j < m; j += BT) xs[swz(Kz + j)] = L.wb[woff + j];
     }
     KTW(9);
     __syncthreads();
     const uint32_t z1 = Kz + m;
     if (t == 0) KT(7);
-    // ── the verdict ──
+    // ── the verdict: the churn workgroup's word (ref mode; the body workgroups' poll) ──
     bool rej = false;
     if (!EXACT) {
-        if (t == 0) rej = s_rej != 0u || *lt.ovf != 0u || lds_find(lt, pid2) != 0u;
-#pragma unroll
-        for (int k = 0; k < KV; ++k) {
-            if (!vq[k] || vq[k] == pid2) continue;
-            const uint32_t d = lds_find(lt, vq[k]);
-            if ((int32_t)d <= 0) continue;
-            uint32_t cnt = 0;
-            if (vq[k] != pid1) {
-                if ((uint32_t)vh[k] == vq[k]) {
-                    cnt = (uint32_t)(vh[k] >> 32);
-                } else {
-                    const uint32_t idx = table_find(tb, vq[k]);
-                    cnt = idx == 0xFFFFFFFFu ? 0u : __hip_atomic_load(&tb.slots[idx].y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (t == 0) {
+            const uint32_t tag = gs.epoch << 2;
+            for (uint32_t it = 0;; ++it) {
+                if ((pv & ~3u) == tag && (pv & 2u)) break;
+                if (it > ZSEG_SPIN) {
+                    atomicOr(&st->err, ERR_SPIN);
+                    pv = 2u;
+                    break;
                 }
-                if ((int32_t)cnt < 0) cnt = 0;
+                __builtin_amdgcn_s_sleep(1);
+                pv = __hip_atomic_load(pair_word(zg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
-            const uint64_t c2 = (uint64_t)cnt + d;
-            if (c2 > mc2 || (c2 == mc2 && vq[k] < pid2)) rej = true;
+            rej = !(pv & 1u);
+            KT(8);
         }
-        // tests (GBPE_DEBUG prej): every prej-th candidate is turned down after the verdict above ran
-        // (gs: the launch's snapshot of the state; only this workgroup counts candidates)
-        if (t == 0 && prej && gs.pair_cand % prej == prej - 1u) rej = true;
         rej = __syncthreads_or(rej) != 0;
-    }
-    if (t == 0) {
-        st->pair_cand += 1u;   // (the stats' pair_candidates / pair_rejected: one zone workgroup per launch)
-        if (rej) st->pair_rej += 1u;
-        if (!rej) {   // commit P2: every occurrence is a site of the second merge
-            const uint32_t idx = (uint32_t)h2 == pid2 ? h2i : table_find(tb, pid2);
-            if (idx == 0xFFFFFFFFu) {
-                atomicOr(&st->err, ERR_PAIR_MISSING);
-            } else {
-                atomicSub(&tb.slots[idx].y, mc2);
-                tb.dirty[idx >> BLK_LOG2] = 1u;
-            }
-            st->acc2 = 1u;
+    } else if (t == 0) {
+        st->pair_cand += 1u;   // (the stats' pair_candidates: one zone workgroup per launch)
+        // commit P2: every occurrence is a site of the second merge
+        const uint32_t idx = (uint32_t)h2 == pid2 ? h2i : table_find(tb, pid2);
+        if (idx == 0xFFFFFFFFu) {
+            atomicOr(&st->err, ERR_PAIR_MISSING);
+        } else {
+            atomicSub(&tb.slots[idx].y, mc2);
+            tb.dirty[idx >> BLK_LOG2] = 1u;
         }
-        __hip_atomic_store(pair_word(zg), (gs.epoch << 2) | (rej ? 2u : 3u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        st->acc2 = 1u;
+        __hip_atomic_store(pair_word(zg), (gs.epoch << 2) | 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         KT(8);
     }
     // the LDS zone's swizzled part [from, tot) to dst as 16-byte vectors (from: a swizzle-group boundary)
@@ -1390,11 +1499,15 @@ struct BodyCandT {
     uint2 ext[CAP];
 };
 using BodyCand = BodyCandT<SP_CAP>;
-// the zone workgroup's LDS (+ in the paired form its own delta table: merge 1's
+// the zone workgroup's LDS (+ in the paired form its own delta table: a merge's
 // stale tail and window are ~2 mc distinct pairs, up to ~3.3K at the form's largest
-// zones, which the 1,024-slot table shared with the body overflowed into global adds)
+// zones, which the 1,024-slot table shared with the body overflowed into global adds;
+// the churn workgroup of a reference-mode paired launch uses the same union for
+// merge 1's tail, window source and table)
 // (u32 zones: 2,048 slots, so two workgroups still fit a CU's LDS — the paired form's
-// grid is the CU count + 1)
+// grid is the CU count + 2 (zone, churn, body), resident at once at two workgroups
+// per CU: the zone and the body workgroups wait on the churn workgroup, which waits
+// on nobody, and blocks 0 and 1 are dispatched first)
 template <typename S> constexpr int zp_lt() { return sizeof(S) == 2 ? 4096 : 2048; }
 template <typename S, int BT, int ZLT>
 struct ZoneWg {
@@ -1455,6 +1568,9 @@ __global__ __launch_bounds__(BT) void k_body(DevState* st, uint32_t round, S* __
     const Table& xtb = dtb;
     SelShard shx = sh;
     if (!PAIR) shx.k2 = 0u;
+    // reference compaction: a launch pairs only with its churn workgroup (pair_churn), which gives the verdict
+    constexpr bool CHURN = PAIR && !EXACT && !ZP_OFF;
+    if (CHURN && !shx.churn) shx.k2 = 0u;
     if (!sel_inline<BT, PAIR>(st, zst, part, npart, EXACT, zone1 != 0, tb, log, grpsum, a, b, nw, mc, md, s2, gs, zs, shx)) {
         return;
     }
@@ -1463,7 +1579,22 @@ __global__ __launch_bounds__(BT) void k_body(DevState* st, uint32_t round, S* __
     S* const zoth = (md & 1u) ? zb0 : zb1;
     // the zone workgroup is dispatched first (block 0 when zone1): it is the longest
     // single chain of the merge, and later blocks of a large grid start later
-    const uint32_t bid = blockIdx.x - zone1;
+    // (a reference-mode paired launch: block 1 is the churn workgroup)
+    const uint32_t nchurn = CHURN ? shx.churn : 0u;
+    const uint32_t bid = blockIdx.x - zone1 - nchurn;
+    if constexpr (CHURN) {
+        if (nchurn && blockIdx.x == 1) {
+            if (s2.dbl) {
+                pair_churn<S, BT, zp_lt<S>()>(st, *gs, zs->n, zcur, zoth, zg, u.zw.z, u.zw.lt, xtb, a, b, nw, mc, s2,
+                                              wg_bytes + nbody, round, shx.prej);
+                if (t == 0) {
+                    KT(5);
+                    KTV(6, 4);
+                }
+            }
+            return;
+        }
+    }
     if constexpr (ZSEG) {
         if (blockIdx.x < zone1) {
             zone_seg<S, EXACT, BT, KB_LT, ZPT>(st, zst, *gs, *zs, zcur, zoth, zg, zone1, u.zw.z, lt, dtb, a, b, nw, mc,
@@ -1480,8 +1611,7 @@ __global__ __launch_bounds__(BT) void k_body(DevState* st, uint32_t round, S* __
             if constexpr (PAIR && !ZP_OFF) {
                 if (s2.dbl) {
                     zone_two<S, EXACT, BT, zp_lt<S>(), ZPT>(st, zst, *gs, zs->n, zcur, zoth, zg, u.zw.z, u.zw.wb2,
-                                                            u.zw.lt, xtb, a, b, nw, mc, s2, wg_bytes + nbody, round,
-                                                            shx.prej);
+                                                            u.zw.lt, xtb, a, b, nw, mc, s2, wg_bytes + nbody, round);
                     two = true;
                 }
             }

@@ -401,13 +401,16 @@ int launch_merge_sparse(gbpe_trainer* t, uint32_t round, hipStream_t s, const Sp
     if (timing) TR_HIP(t, hipEventRecord(ev[1], s));   // selection runs inside k_body (sel_inline)
     // zone segments run inside k_body (its ZSEG form)
     const bool inbody = g.zone1 >= 2;
-    const uint32_t gb = g.body + (g.zone1 ? g.zone1 : g.copy);
     const uint32_t z1 = g.zone1;   // k_body's own zone workgroups
     const int bt = inbody ? (g.seg8 ? 2049 : 2048) : g.bt;
     SelShard sh;
     sh.sub = g.sub;
     sh.k2 = g.pair ? 1u : 0u;
     sh.prej = t->pair_prej;
+    // a paired launch under the reference compaction: block 1 is the churn workgroup (pair_churn),
+    // right after the zone workgroup; both add their bytes to the counter after the body's
+    sh.churn = (g.pair && !exact && !ZP_OFF && bt == 256 && z1 == 1) ? 1u : 0u;
+    const uint32_t gb = g.body + (g.zone1 ? g.zone1 : g.copy) + sh.churn;
     if ((uint64_t)g.body + 1 > t->wg_bytes.cap)   // k_body's per-workgroup byte counters (and the zone's after them)
         return gbpe_set_error(t->ctx, GBPE_E_INTERNAL, "k_body grid (%u) above its byte counters (%llu)", g.body,
                               (unsigned long long)t->wg_bytes.cap);

@@ -80,7 +80,9 @@ for name in sys.argv[4:]:
                               "merges": int(m.shape[0]), "equal": eq,
                               "sparse_exits": int(st.sparse_exits),
                               "table_slots": int(st.table_slots), "max_live_pairs": int(st.max_live_pairs),
-                              "paired": int(getattr(st, "paired_merges", 0))}), flush=True)
+                              "paired": int(getattr(st, "paired_merges", 0)),
+                              "pair_candidates": int(getattr(st, "pair_candidates", 0)),
+                              "pair_rejected": int(getattr(st, "pair_rejected", 0))}), flush=True)
         if not eq:
             print(json.dumps({"name": name, "error": "merges differ from the fixture"}), flush=True)
             sys.exit(3)

@@ -9,5 +9,5 @@ for u in train train_lexshard; do
 done
 wait
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 build/api.o build/$1/train.o \
-  build/$1/train_lexshard.o build/encode.o build/pretok.o build/host_io.o build/merge_encode.o -o lib/$1/libgpubpe.so
+  build/$1/train_lexshard.o build/encode.o build/pretok.o build/host_io.o build/merge_encode.o build/decode.o -o lib/$1/libgpubpe.so
 echo "lib/$1/libgpubpe.so"
