@@ -145,6 +145,14 @@ hipError_t gbpe_dev_malloc(gbpe_ctx* ctx, void** p, uint64_t bytes) {
     return e;
 }
 
+// why the last gbpe_ctx_create failed: there is no context to hold the text, so
+// gbpe_last_error(NULL) returns it
+static std::string g_create_err;
+static int create_err(int code, const std::string& msg) {
+    g_create_err = msg;
+    return code;
+}
+
 extern "C" {
 
 const char* gbpe_version(void) { return "gpubpe 0.8 (gfx950, abi 8)"; }
@@ -165,15 +173,19 @@ int gbpe_ctx_create(int device_ordinal, gbpe_ctx** out) {
     *out = nullptr;
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
-    if (e != hipSuccess || count == 0) return GBPE_E_DEVICE;
-    if (device_ordinal < 0 || device_ordinal >= count) return GBPE_E_INVALID;
+    if (e != hipSuccess || count == 0) return create_err(GBPE_E_DEVICE, "no HIP device");
+    if (device_ordinal < 0 || device_ordinal >= count)
+        return create_err(GBPE_E_INVALID, "device " + std::to_string(device_ordinal) + " of " + std::to_string(count));
+    // the knobs are read from here on (poison with the first pool block)
+    const std::string bad = gbpe_debug_unknown();
+    if (!bad.empty()) return create_err(GBPE_E_INVALID, "GBPE_DEBUG: unknown key '" + bad + "'");
     auto* ctx = new (std::nothrow) gbpe_ctx();
-    if (!ctx) return GBPE_E_OOM;
+    if (!ctx) return create_err(GBPE_E_OOM, "out of host memory");
     ctx->device = device_ordinal;
     if (hipSetDevice(device_ordinal) != hipSuccess ||
         hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
         delete ctx;
-        return GBPE_E_DEVICE;
+        return create_err(GBPE_E_DEVICE, "hipSetDevice / hipStreamCreate failed");
     }
     ctx->own_stream = ctx->stream;
     hipDeviceProp_t prop;
@@ -185,7 +197,7 @@ int gbpe_ctx_create(int device_ordinal, gbpe_ctx** out) {
     if (hipHostMalloc((void**)&ctx->enc_host_total, 64, hipHostMallocDefault) != hipSuccess) {
         hipStreamDestroy(ctx->stream);
         delete ctx;
-        return GBPE_E_OOM;
+        return create_err(GBPE_E_OOM, "out of pinned host memory");
     }
     *out = ctx;
     return GBPE_OK;
@@ -237,7 +249,9 @@ int gbpe_ctx_limits(gbpe_ctx* ctx, uint64_t* max_buffer_size) {
     return GBPE_OK;
 }
 
-const char* gbpe_last_error(const gbpe_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
+const char* gbpe_last_error(const gbpe_ctx* ctx) {
+    return ctx ? ctx->err.c_str() : g_create_err.empty() ? "null context" : g_create_err.c_str();
+}
 
 int gbpe_ctx_trim(gbpe_ctx* ctx) {
     if (!ctx) return GBPE_E_INVALID;

@@ -144,6 +144,11 @@ __host__ __device__ static inline uint64_t gbpe_div_up(uint64_t a, uint64_t b) {
 
 // Debug / test overrides: GBPE_DEBUG="key=value,key=value" (DESIGN §6 lists the
 // keys); every other tuning value is a compiled default
+constexpr const char* kGbpeDebugKeys[] = {
+    "lexicon", "lex_check", "rehash", "delta_mt", "zt", "rfl", "rflz", "lxwg", "lxtwo", "pair", "prej", "poison",
+    "encode_slice", "decode_slice", "dec_plain", "htime", "ptrace", "rtime",
+};
+
 inline long gbpe_debug_knob(const char* key, long def) {
     const char* e = getenv("GBPE_DEBUG");
     if (!e) return def;
@@ -155,6 +160,21 @@ inline long gbpe_debug_knob(const char* key, long def) {
         p = c + 1;
     }
     return def;
+}
+
+// the key of the first GBPE_DEBUG entry that is not `<key of kGbpeDebugKeys>=value`
+// ("" when every entry is; empty entries between commas pass): context and trainer
+// creation refuse it, so that a misspelt or retired key cannot pass for the default
+inline std::string gbpe_debug_unknown() {
+    const char* e = getenv("GBPE_DEBUG");
+    for (const char* p = e ? e : ""; *p;) {
+        const size_t el = strcspn(p, ","), kl = strcspn(p, ",=");
+        bool ok = el == 0;
+        for (const char* k : kGbpeDebugKeys) ok = ok || (kl < el && strlen(k) == kl && !strncmp(p, k, kl));
+        if (!ok) return std::string(p, kl ? kl : el);   // ("=1": the entry)
+        p += el + (p[el] == ',');
+    }
+    return "";
 }
 
 // GPT-4 rule word starts of device bytes on ctx->stream (pretok.hip)

@@ -35,8 +35,17 @@ constexpr uint32_t SP_SHRINKS = 64;  // zone shrinks per sparse entry the first 
 constexpr uint32_t SP_SHRINKS_MAX = 1024;   // zone shrinks per sparse entry
 constexpr uint32_t SP_SECW = 256;        // sector window (symbols)
 constexpr uint32_t SP_DIV = 64;          // without the lexicon: enter when last_mc * SP_DIV <= n
+constexpr uint32_t SP_LX_DIV = 16;       // with the lexicon: enter once next_mc * SP_LX_DIV <= n, from the first step on
 constexpr uint32_t SP_SHRINK_PCT = 200;  // shrink once the zone exceeds SP_SHRINK_PCT % of the target + 4096
 constexpr uint32_t SP_ZONE_F = 3;        // single-GPU zone rule factor (sel_inline, >= 3)
+constexpr uint32_t SP_SUB_ZONE = 1u << 20;   // sparse steps run in sub-steps of SP_SUB_K merges while the zone exceeds this
+constexpr uint32_t SP_SUB_K = 16;            // (the zone shrinks between them)
+constexpr uint32_t SP_ZSEG_LO = 8192;    // zones above this many symbols run as zone segments (16384 = round 4:
+                                         // 1 GiB 0.557 vs 0.548 s, C2 equal, C1 11.6 vs 11.8 ms, profiles/r5/s30)
+constexpr uint32_t SP_BODY_SUB = 4;      // most k_body workgroups per bitmap word (1, 2, 4;
+                                         // C1 13.5 -> 11.9 ms at 4, profiles/r5/s21)
+constexpr uint32_t SP_BODY_MIN = 256;    // k_body workgroups at least, one bitmap word each at most
+                                         // (1 = the round-4 sizing of >= 16 / 32 words per workgroup)
 
 // Per-sector pair signature: a 2048-bit Bloom filter (3 hash bits) of every pair
 // the sector has held since the filters were last rebuilt.  The token bitmap
@@ -46,28 +55,7 @@ constexpr uint32_t SP_ZONE_F = 3;        // single-GPU zone rule factor (sel_inl
 // pairs plus those its merges add — and every false candidate costs a sector
 // pass: 2048 / 3 cuts that rate to a few percent.)
 constexpr uint32_t SP_SIGW = 64;     // u32 words per sector signature
-#ifdef GBPE_SIG_GLOBAL
-constexpr bool SIG_LDS = false;      // (A/B build: every created pair's bits straight to the global signature)
-#else
-constexpr bool SIG_LDS = true;       // k_body gathers a sector's new signature bits in LDS (body_sector's lsig)
-#endif
-constexpr uint32_t SP_SIGB = SP_SIGW * 32 - 1;
 __device__ __forceinline__ uint32_t sig_hash(uint32_t pid) { return gbpe_fmix32(pid ^ 0x9E3779B9u); }
-#ifdef GBPE_SIG_SPREAD
-// (A/B build: the three bits anywhere in the 2048 — a test loads up to three
-// words on two 128-B lines)
-__device__ __forceinline__ void sig_bits(uint32_t pid, uint32_t& b1, uint32_t& b2, uint32_t& b3) {
-    const uint32_t h = sig_hash(pid), h2 = h * 0x9E3779B1u;
-    b1 = h & SP_SIGB;
-    b2 = (h >> 16) & SP_SIGB;
-    b3 = (h2 >> 21) & SP_SIGB;
-}
-__device__ __forceinline__ bool sig_has(const uint32_t* __restrict__ sig, uint32_t pid) {
-    uint32_t b1, b2, b3;
-    sig_bits(pid, b1, b2, b3);
-    return ((sig[b1 >> 5] >> (b1 & 31u)) & (sig[b2 >> 5] >> (b2 & 31u)) & (sig[b3 >> 5] >> (b3 & 31u)) & 1u) != 0u;
-}
-#else
 // Blocked: the hash picks one 64-bit word of the 32, and the three bits inside
 // it, so a candidate test is ONE 8-byte load (one line) instead of up to three
 // words on two lines (the filter's false-positive rate at ~300 pairs per sector
@@ -84,7 +72,6 @@ __device__ __forceinline__ bool sig_has(const uint32_t* __restrict__ sig, uint32
     const uint64_t m = (1ull << ((h >> 5) & 63u)) | (1ull << ((h >> 11) & 63u)) | (1ull << ((h >> 17) & 63u));
     return (v & m) == m;
 }
-#endif
 // global signature (k_body): no-return atomics, no test load on the merge's critical path
 __device__ __forceinline__ void sig_or(uint32_t* __restrict__ sig, uint32_t pid) {
     uint32_t b1, b2, b3;
@@ -1486,11 +1473,6 @@ __device__ __forceinline__ void zone_two(DevState* st, DevState* zst, const DevS
 // merges, merges the first's candidate sectors, then — once the zone workgroup
 // accepted the second (ref mode) — the second's.  A sector is owned by one
 // workgroup for both, so its two merges run in order.
-#ifdef GBPE_ZP_OFF
-constexpr bool ZP_OFF = true;
-#else
-constexpr bool ZP_OFF = false;
-#endif
 constexpr uint32_t SP_PW = 64;               // bitmap words tested per pass (one per lane of wave 0)
 constexpr uint32_t SP_CAP = SP_PW * 32;      // candidate sectors per pass
 template <uint32_t CAP>
@@ -1542,12 +1524,7 @@ __global__ __launch_bounds__(BT) void k_body(DevState* st, uint32_t round, S* __
     __shared__ BodyLds<S, BT, PAIR ? zp_lt<S>() : 1> u;
     // per wave: its sector's new signature bits (the 1024-thread forms: the early,
     // site-heavy merges; the 256-thread late form keeps 4 waves per SIMD without it)
-    constexpr bool SIGL = SIG_LDS && BT == 1024;
-#ifdef GBPE_NO_SINK
-    constexpr bool SINK = false;
-#else
-    constexpr bool SINK = true;   // body_sector waits for the next sector's prefetch before its stores
-#endif
+    constexpr bool SIGL = BT == 1024;
     __shared__ uint32_t s_sig[SIGL ? BT / 64 : 1][SP_SIGW];
     __shared__ uint32_t s_ntok2, s_ntok1, s_n, s_n2, s_any, s_acc, s_rm[BT / 64], s_rm2[BT / 64];
     __shared__ uint32_t s_hit1[PAIR ? SP_CAP / 32 : 1];   // sectors the first merge changed (local index bits)
@@ -1569,7 +1546,7 @@ __global__ __launch_bounds__(BT) void k_body(DevState* st, uint32_t round, S* __
     SelShard shx = sh;
     if (!PAIR) shx.k2 = 0u;
     // reference compaction: a launch pairs only with its churn workgroup (pair_churn), which gives the verdict
-    constexpr bool CHURN = PAIR && !EXACT && !ZP_OFF;
+    constexpr bool CHURN = PAIR && !EXACT;
     if (CHURN && !shx.churn) shx.k2 = 0u;
     if (!sel_inline<BT, PAIR>(st, zst, part, npart, EXACT, zone1 != 0, tb, log, grpsum, a, b, nw, mc, md, s2, gs, zs, shx)) {
         return;
@@ -1608,7 +1585,7 @@ __global__ __launch_bounds__(BT) void k_body(DevState* st, uint32_t round, S* __
     } else {
         if (zone1 == 1 && blockIdx.x == 0) {
             bool two = false;
-            if constexpr (PAIR && !ZP_OFF) {
+            if constexpr (PAIR) {
                 if (s2.dbl) {
                     zone_two<S, EXACT, BT, zp_lt<S>(), ZPT>(st, zst, *gs, zs->n, zcur, zoth, zg, u.zw.z, u.zw.wb2,
                                                             u.zw.lt, xtb, a, b, nw, mc, s2, wg_bytes + nbody, round);
@@ -1807,10 +1784,11 @@ __global__ __launch_bounds__(BT) void k_body(DevState* st, uint32_t round, S* __
                     en = ext_of(j + BT / 64);
                     sector_first<S>(body + en.x, lmul ? lmul + en.x : nullptr, en.y, nf, nfm);
                 }
+                // (nf / nfm: body_sector waits for the next sector's prefetch before its stores)
                 uint32_t out = 0;
                 const uint32_t r = body_sector<S, KB_LT, Table, LdsTab<KB_LT>, SIGL>(
                     body + e.x, lmul ? lmul + e.x : nullptr, e.y, ca, cbb, cn, lt, xtb, st, sig + (uint64_t)sct * SP_SIGW,
-                    out, cf, cfm, s_sig[SIGL ? wid : 0], SINK ? nf : nullptr, SINK ? nfm : nullptr BSP_PASS);
+                    out, cf, cfm, s_sig[SIGL ? wid : 0], nf, nfm BSP_PASS);
                 moved += (uint64_t)(sizeof(S) + (lmul ? 4u : 0u)) * (e.y + (r ? out : 0u));
                 if (r) {
                     if (ph) removed2 += r;

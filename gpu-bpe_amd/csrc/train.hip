@@ -48,7 +48,10 @@ int trainer_create_impl(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, const u
     const auto t_create0 = std::chrono::steady_clock::now();
     auto* t = new (std::nothrow) gbpe_trainer();
     if (!t) return gbpe_set_error(ctx, GBPE_E_OOM, "host allocation failed");
-    trainer_config(t, ctx, opts);
+    if (const int rc = trainer_config(t, ctx, opts)) {   // (an unknown GBPE_DEBUG key: nothing allocated yet)
+        delete t;
+        return rc;
+    }
     const uint32_t next_id = t->next_id0;
     t->bps = t->u16 ? 2 : 4;
     t->n0 = n;
@@ -214,11 +217,13 @@ int trainer_step_once(gbpe_trainer* t, uint32_t max_merges, uint32_t* merges_out
     hipStream_t s = t->ctx->stream;
     // rebuild the pair table when it gets crowded (dead pairs accumulate), twice as
     // large (or more) while the live pairs would fill over a quarter of it
+    constexpr uint32_t GROW_USED_PCT = 50;   // the table is rebuilt once its occupied slots (dead included) pass this %
+    constexpr uint32_t GROW_LIVE_PCT = 25;   // ... into the smallest 2^k slots its live pairs fill to at most this %
     const uint64_t slots = (uint64_t)t->tb.mask + 1;
-    if ((uint64_t)t->h_st->used * 100 > slots * t->grow_used_pct) {
+    if ((uint64_t)t->h_st->used * 100 > slots * GROW_USED_PCT) {
         const uint64_t live = std::max<uint64_t>(t->h_st->live, t->h_st->used / 2);
         uint32_t lg = t->table_log2;
-        while (lg < 28 && live * 100 > (1ull << lg) * t->grow_live_pct) ++lg;
+        while (lg < 28 && live * 100 > (1ull << lg) * GROW_LIVE_PCT) ++lg;
         int rc;
         if (t->sp && t->rehash_on) {   // the sparse loop goes on over the moved entries
             rc = table_rehash(t, lg);
@@ -250,7 +255,7 @@ int trainer_step_once(gbpe_trainer* t, uint32_t max_merges, uint32_t* merges_out
             TR_HIP(t, hipStreamSynchronize(s));
             mc = next;
         }
-        const uint64_t div = t->lex_on ? t->lx_div : SP_DIV;
+        const uint64_t div = t->lex_on ? SP_LX_DIV : SP_DIV;
         const bool count_ok = mc && ((t->flags & GBPE_TRAIN_SPARSE_EARLY) || (uint64_t)mc * div <= t->n);
         if (count_ok) {
             int rc = t->u16 ? sp_enter<uint16_t>(t, true, next) : sp_enter<uint32_t>(t, true, next);
@@ -289,8 +294,8 @@ int trainer_step_once(gbpe_trainer* t, uint32_t max_merges, uint32_t* merges_out
     // costs milliseconds there; every round the step enqueues after the entry point
     // would still launch its full-grid kernels as no-ops)
     if (!t->sp && t->h_st->enter_lim && t->n >= (1u << 24)) k = 1;
-    // a large zone shrinks every sub_k merges instead of every step (early counts fall fast)
-    if (t->sp && (uint32_t)t->n - t->h_st->B > t->sub_zone && k > t->sub_k) k = t->sub_k;
+    // a large zone shrinks every SP_SUB_K merges instead of every step (early counts fall fast)
+    if (t->sp && (uint32_t)t->n - t->h_st->B > SP_SUB_ZONE && k > SP_SUB_K) k = SP_SUB_K;
     // reset the per-step counter + budget (trainer.js:239)
     DevState* hs = t->h_st.p;
     hs->merges_done = 0;
@@ -324,13 +329,13 @@ int trainer_step_once(gbpe_trainer* t, uint32_t max_merges, uint32_t* merges_out
         const uint32_t zn = (uint32_t)t->n - hs->B;   // zone length (it only shrinks within a step)
         const uint64_t zt = gbpe_div_up(zn, TILE);
         const uint32_t z256 = t->u16 ? zone_max<uint16_t>(256) : zone_max<uint32_t>(256);
-        sg.bt = zn <= std::min<uint32_t>(z256, t->z256) ? 256 : 1024;   // small zone: the low-latency 256-thread workgroups
+        sg.bt = zn <= z256 ? 256 : 1024;   // small zone: the low-latency 256-thread workgroups
         body_grid(t, sg.bt, &sg.body, &sg.wpg, 0, &sg.sub);
         if (sg.bt == 1024 && t->u16 && zn <= 16384u) sg.bt = 1023;
         sg.zone1 = zn <= (t->u16 ? zone_max<uint16_t>(sg.bt) : zone_max<uint32_t>(sg.bt)) ? 1u : 0u;
         // a zone of 16K-1M symbols: 16K-symbol segments inside k_body (its ZSEG form)
-        if (t->zseg.p && zn > t->zseg_lo && zn <= NSEG_MAX * 16384u) {
-            sg.seg8 = t->seg8 && zn <= NSEG_MAX * 8192u;
+        if (t->zseg.p && zn > SP_ZSEG_LO && zn <= NSEG_MAX * 16384u) {
+            sg.seg8 = zn <= NSEG_MAX * 8192u;
             sg.zone1 = (uint32_t)gbpe_div_up(zn, sg.seg8 ? 8192u : 16384u);
         }
         sg.copy = (t->flags & GBPE_TRAIN_EXACT_COMPACTION) ? 0u : grid_persistent(t->ctx, gbpe_div_up(zn / 5 + 1, TPB * 8), 1);
@@ -342,7 +347,7 @@ int trainer_step_once(gbpe_trainer* t, uint32_t max_merges, uint32_t* merges_out
         // a CU to drain (C5 merges 512-8K: the last one started 14-19 us late) — so
         // the body takes the CUs the others leave
         const uint32_t extra = sg.zone1 ? sg.zone1 : sg.copy;
-        if (sg.bt >= 1023 && t->body_fit && extra && sg.body + extra > t->body_cap && 2 * extra <= t->body_cap)
+        if (sg.bt >= 1023 && extra && sg.body + extra > t->body_cap && 2 * extra <= t->body_cap)
             body_grid(t, sg.bt, &sg.body, &sg.wpg, t->body_cap - extra, &sg.sub);
         // late steps (a zone of <= 16K symbols): a smaller k_refresh grid —
         // a late merge dirties a few blocks, and fewer workgroups dispatch and drain

@@ -366,7 +366,10 @@ extern "C" int gbpe_trainer_create_from_lexicon(gbpe_ctx* ctx, const void* store
     if (zone_len == 0) return gbpe_set_error(ctx, GBPE_E_INVALID, "lexicon hand-over: the stream's tail must be a zone");
     auto* t = new (std::nothrow) gbpe_trainer();
     if (!t) return gbpe_set_error(ctx, GBPE_E_OOM, "host allocation failed");
-    trainer_config(t, ctx, opts);
+    if (const int rc = trainer_config(t, ctx, opts)) {   // (an unknown GBPE_DEBUG key: nothing allocated yet)
+        delete t;
+        return rc;
+    }
     t->lex_only = true;
     t->n0 = t->n = body_len + zone_len;
     hipStream_t s = ctx->stream;

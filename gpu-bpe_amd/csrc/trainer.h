@@ -65,8 +65,6 @@ struct gbpe_trainer {
     GbpeArray<DevState, true> h_zst;
     GbpeArray<uint32_t> d_u32;   // small device scratch
     GbpeArray<uint64_t> part;    // k_refresh workgroup maxima (sparse selection)
-    uint32_t grow_used_pct = 50;   // the table is rebuilt once its occupied slots (dead included) pass this %
-    uint32_t grow_live_pct = 25;   // ... into the smallest 2^k slots its live pairs fill to at most this %
     GbpeArray<uint2> zdr_out;    // the multi-tile zone passes' delta dumps (ZdrView, train_dev.h)
     GbpeArray<uint32_t> zdr_offs, zdr_flag;
     uint32_t zdr_ntile = 0;      // tile-workgroup dumps the buffers hold (+ ZDR_P churn workgroups)
@@ -83,30 +81,17 @@ struct gbpe_trainer {
     uint32_t sp_enters = 0, sp_exits = 0;
     uint32_t sp_cooldown = 0;    // steps to stay dense after an abort
     GbpeArray<uint32_t> d_bhist; // byte-pair histogram of the first count (65,536 u32)
-    uint32_t seg8 = 1;           // zone segments of 8K symbols for zones <= 512K (GBPE_DEBUG seg8; 0: 16K)
-    uint32_t zseg_lo = 8192;     // zones above this many symbols run as zone segments (GBPE_DEBUG zslo; 16384
-                                 // = round 4: 1 GiB 0.557 vs 0.548 s, C2 equal, C1 11.6 vs 11.8 ms, profiles/r5/s30)
-    uint32_t z256 = 0xFFFFFFFFu; // largest zone for the 256-thread k_body form (GBPE_DEBUG z256; 0: always 1024)
-    uint32_t body_sub = 4;       // most k_body workgroups per bitmap word (1, 2, 4; GBPE_DEBUG bsub;
-                                 // C1 13.5 -> 11.9 ms at 4, profiles/r5/s21)
-    uint32_t body_min = 256;     // k_body workgroups at least, one bitmap word each at most (GBPE_DEBUG bmin;
-                                 // 1 = the round-4 sizing of >= 16 / 32 words per workgroup)
     uint32_t lx_wg = 16384;      // k_lx_hash workgroups (at least LX_WPT words per thread; GBPE_DEBUG lxwg)
     bool lx_two = true;          // two-stage word-table build for large segments (GBPE_DEBUG lxtwo=0: one stage)
     uint32_t lx_resize = 0;      // builds whose sampled table was too small (rerun at full size)
-    uint32_t lx_div = 16;        // with the lexicon: enter once next_mc * lx_div <= n, from the first step on (GBPE_DEBUG lxdiv)
-    uint32_t sub_zone = 1u << 20;   // sparse steps run in sub-steps of sub_k merges while the zone exceeds this
-    uint32_t sub_k = 16;            // (the zone shrinks between them; GBPE_DEBUG subz, subk)
     uint32_t sp_zt = 5;          // zone target = sp_zt * last_mc + 64 (>= SP_ZONE_F; GBPE_DEBUG zt; 4/5/6/7 measured
                                  // 0.895/0.893/0.918/0.918 s at 1 GiB with SP_ZONE_F 3)
-    uint32_t refresh_blocks = 0; // k_refresh grid (0 = 2 per CU)
-    uint32_t refresh_late_z = 16384; // ... for zones of at most this many symbols
-    uint32_t refresh_late = 64;  // k_refresh grid of late steps (0 = unchanged)
+    uint32_t refresh_late = 64;  // k_refresh grid of late steps (0 = unchanged: 2 per CU; GBPE_DEBUG rfl)
+    uint32_t refresh_late_z = 16384; // ... for zones of at most this many symbols (GBPE_DEBUG rflz)
     bool rehash_on = true;       // grow the table inside the sparse loop (GBPE_DEBUG rehash=0: exit, grow, recount)
-    uint32_t body_cap = 256;     // most k_body workgroups (one per CU)
-    bool body_fit = true;        // the body's workgroups leave the zone's their CUs (GBPE_DEBUG bodyfit=0: off)
+    uint32_t body_cap = 256;     // most k_body workgroups: one per CU, measured best at 1 GiB
+                                 // (128/192/256/384/512/1024: 3.01/2.42/2.14/2.66/2.45/2.98 s)
     bool pair_on = true;         // paired launches (GBPE_DEBUG pair=0: one merge per launch)
-    bool pair_one = true;        // zones just above the zone_one form shrink into it (GBPE_DEBUG pone)
     double pair_rate = 0.5;      // second merges per launch of the last paired step (sizes the next step's launches)
     uint64_t pair_done = 0;      // merges run as the second of a launch (stats)
     uint32_t pair_prej = 0;      // GBPE_DEBUG prej=k (tests): the verdict rejects every k-th candidate (0: off)
@@ -182,7 +167,6 @@ int table_resize(gbpe_trainer* t, uint32_t lg) {
                   t->tb_dlist.p, t->tb_blive.p, nblk, &t->st->used};
     TR_HIP(t, hipMemsetAsync(t->tb.dirty, 0, nblk * sizeof(uint32_t), s));
     t->g_refresh = grid_blocks(t->ctx, nblk, 2);
-    if (t->refresh_blocks) t->g_refresh = std::max<uint32_t>(t->refresh_blocks, (uint32_t)gbpe_div_up(nblk, 64));
     if (t->part.p) return part_reserve(t);
     return GBPE_OK;
 }
@@ -349,12 +333,12 @@ inline void body_grid(const gbpe_trainer* t, int bt, uint32_t* nbody, uint32_t* 
     const uint32_t W = (uint32_t)gbpe_div_up(t->nsec, 32);
     const uint32_t minw = bt == 1024 ? 32u : 16u;
     uint32_t g = (uint32_t)gbpe_div_up(W, minw);
-    // but at least body_min workgroups (one bitmap word, 32 sectors, each at least):
+    // but at least SP_BODY_MIN workgroups (one bitmap word, 32 sectors, each at least):
     // a word's candidates then spread over more CUs instead of queueing on one
-    // workgroup's waves (round 5, profiles/r5/s20: bmin 1 -> 256 took C1 25.1 ->
+    // workgroup's waves (round 5, profiles/r5/s20: 1 -> 256 took C1 25.1 ->
     // 13.2 ms, C2 0.470 -> 0.428 s, 1 GiB 0.602 -> 0.568 s; C5 unchanged — its
     // 131K-sector bitmap rows already fill every CU)
-    const uint32_t gmin = std::min<uint32_t>(W, t->body_min);
+    const uint32_t gmin = std::min<uint32_t>(W, SP_BODY_MIN);
     if (g < gmin) g = gmin;
     if (g > (cap ? cap : t->body_cap)) g = cap ? cap : t->body_cap;
     if (g == 0) g = 1;
@@ -365,7 +349,7 @@ inline void body_grid(const gbpe_trainer* t, int bt, uint32_t* nbody, uint32_t* 
     if (sub) {   // a row of few words: 2 or 4 workgroups per word (slices of 16 / 8 sectors)
         *sub = 1;
         const uint32_t c = cap ? cap : t->body_cap;
-        while (*sub * 2 <= t->body_sub && (uint64_t)W * *sub * 2 <= c) *sub *= 2;
+        while (*sub * 2 <= SP_BODY_SUB && (uint64_t)W * *sub * 2 <= c) *sub *= 2;
         if (*sub > 1) {
             *wpg = 1;
             *nbody = W * *sub;
@@ -409,7 +393,7 @@ int launch_merge_sparse(gbpe_trainer* t, uint32_t round, hipStream_t s, const Sp
     sh.prej = t->pair_prej;
     // a paired launch under the reference compaction: block 1 is the churn workgroup (pair_churn),
     // right after the zone workgroup; both add their bytes to the counter after the body's
-    sh.churn = (g.pair && !exact && !ZP_OFF && bt == 256 && z1 == 1) ? 1u : 0u;
+    sh.churn = (g.pair && !exact && bt == 256 && z1 == 1) ? 1u : 0u;
     const uint32_t gb = g.body + (g.zone1 ? g.zone1 : g.copy) + sh.churn;
     if ((uint64_t)g.body + 1 > t->wg_bytes.cap)   // k_body's per-workgroup byte counters (and the zone's after them)
         return gbpe_set_error(t->ctx, GBPE_E_INTERNAL, "k_body grid (%u) above its byte counters (%llu)", g.body,
@@ -1121,7 +1105,7 @@ int sp_shrink(gbpe_trainer* t) {
     // paired launches run in the zone_one form: a zone just above it whose target fits
     // shrinks into it (else it stays there until z >= 2 zt + 4096: 1 GiB merges ~12K-25K)
     const uint64_t zmax1 = zone_max<S>(256);
-    const bool to_one = t->pair_on && t->pair_one && z > zmax1 && zt + 512 <= zmax1;
+    const bool to_one = t->pair_on && z > zmax1 && zt + 512 <= zmax1;
     if (t->sp_shrinks >= SP_SHRINKS_MAX || ((uint64_t)z < zt * SP_SHRINK_PCT / 100 + 4096 && !to_one)) return GBPE_OK;
     S* zc = (S*)t->zbuf[t->zcur].p;
     S* zo = (S*)t->zbuf[t->zcur ^ 1].p;
@@ -1219,7 +1203,9 @@ int sp_exit(gbpe_trainer* t) {
 }
 
 // options and environment knobs of a new trainer; symbol width from the ids the run can make
-void trainer_config(gbpe_trainer* t, gbpe_ctx* ctx, const gbpe_train_opts* opts) {
+int trainer_config(gbpe_trainer* t, gbpe_ctx* ctx, const gbpe_train_opts* opts) {
+    const std::string bad = gbpe_debug_unknown();
+    if (!bad.empty()) return gbpe_set_error(ctx, GBPE_E_INVALID, "GBPE_DEBUG: unknown key '%s'", bad.c_str());
     t->ctx = ctx;
     t->flags = opts->flags;
     t->batch = opts->batch_size ? opts->batch_size : GBPE_BATCH_SIZE;
@@ -1232,34 +1218,20 @@ void trainer_config(gbpe_trainer* t, gbpe_ctx* ctx, const gbpe_train_opts* opts)
     t->u16 = max_id <= 0x8000ull;
     t->max_id = (uint32_t)(max_id < 0x10000ull ? max_id : 0x10000ull);
     t->body_cap = (uint32_t)(ctx->num_cu > 0 ? ctx->num_cu : 256);
-    t->body_cap = (uint32_t)std::max<long>(1, gbpe_debug_knob("bcap", t->body_cap));
-    t->z256 = (uint32_t)gbpe_debug_knob("z256", t->z256);
-    t->seg8 = (uint32_t)gbpe_debug_knob("seg8", t->seg8);
-    t->zseg_lo = (uint32_t)std::max<long>(8192, gbpe_debug_knob("zslo", t->zseg_lo));   // one per CU: measured best at 1 GiB (128/192/256/384/512/1024: 3.01/2.42/2.14/2.66/2.45/2.98 s)
     // test overrides (GBPE_DEBUG): the lexicon off / its build check, the
     // in-loop table growth off, the multi-tile k_delta threshold, the zone target
     t->lex_on = gbpe_debug_knob("lexicon", 1) != 0;
-    t->body_fit = gbpe_debug_knob("bodyfit", 1) != 0;
     t->pair_on = gbpe_debug_knob("pair", 1) != 0;
-    t->pair_one = gbpe_debug_knob("pone", 1) != 0;
     t->pair_prej = (uint32_t)std::max<long>(0, gbpe_debug_knob("prej", 0));
     t->ptrace = (uint32_t)gbpe_debug_knob("ptrace", 0);
     t->rehash_on = gbpe_debug_knob("rehash", 1) != 0;
     t->delta_mt = (uint32_t)gbpe_debug_knob("delta_mt", t->delta_mt);
     t->sp_zt = (uint32_t)gbpe_debug_knob("zt", t->sp_zt);
-    t->grow_used_pct = (uint32_t)std::min<long>(90, std::max<long>(10, gbpe_debug_knob("gused", t->grow_used_pct)));
-    t->grow_live_pct = (uint32_t)std::min<long>(t->grow_used_pct, std::max<long>(5, gbpe_debug_knob("glive", t->grow_live_pct)));
-    t->refresh_blocks = (uint32_t)gbpe_debug_knob("rfb", t->refresh_blocks);   // k_refresh grid sweeps
-    t->refresh_late = (uint32_t)gbpe_debug_knob("rfl", t->refresh_late);
+    t->refresh_late = (uint32_t)gbpe_debug_knob("rfl", t->refresh_late);   // k_refresh grid sweeps
     t->refresh_late_z = (uint32_t)gbpe_debug_knob("rflz", t->refresh_late_z);
-    t->lx_div = (uint32_t)std::max<long>(1, gbpe_debug_knob("lxdiv", t->lx_div));   // lexicon entry / sub-step sweeps
     t->lx_wg = (uint32_t)std::max<long>(1, gbpe_debug_knob("lxwg", t->lx_wg));
     t->lx_two = gbpe_debug_knob("lxtwo", 1) != 0;
     t->htime = (uint32_t)gbpe_debug_knob("htime", 0);
-    t->body_min = (uint32_t)std::max<long>(1, gbpe_debug_knob("bmin", t->body_min));
-    t->body_sub = (uint32_t)std::min<long>(4, std::max<long>(1, gbpe_debug_knob("bsub", t->body_sub)));
-    t->sub_k = (uint32_t)std::max<long>(1, gbpe_debug_knob("subk", t->sub_k));
-    t->sub_zone = (uint32_t)std::max<long>(1, gbpe_debug_knob("subz", t->sub_zone));
     if (t->sp_zt < SP_ZONE_F) t->sp_zt = SP_ZONE_F;
     if (const char* e = getenv("GBPE_SPARSE_TRACE")) {
         t->trace = fopen(e, "w");
@@ -1268,6 +1240,7 @@ void trainer_config(gbpe_trainer* t, gbpe_ctx* ctx, const gbpe_train_opts* opts)
             t->d_clog.release(), t->h_clog.release();   // trace without candidate counts
     }
     t->bps = t->u16 ? 2 : 4;
+    return GBPE_OK;
 }
 
 int sp_exit_any(gbpe_trainer* t) { return !t->sp ? GBPE_OK : (t->u16 ? sp_exit<uint16_t>(t) : sp_exit<uint32_t>(t)); }

@@ -182,8 +182,6 @@ class GpuBpeError(RuntimeError):
 def check(rc: int, ctx=None, what: str = ""):
     if rc == GBPE_OK:
         return
-    msg = ""
-    if ctx is not None:
-        raw = load().gbpe_last_error(ctx)
-        msg = raw.decode("utf-8", "replace") if raw else ""
+    raw = load().gbpe_last_error(ctx)   # (ctx None: why gbpe_ctx_create failed)
+    msg = raw.decode("utf-8", "replace") if raw else ""
     raise GpuBpeError(rc, f"{what}: {msg or 'gpubpe error'} (status {rc})")

@@ -29,7 +29,8 @@ class BPEEngine:
         ctx = C.c_void_p()
         rc = lib.gbpe_ctx_create(self._device, C.byref(ctx))
         if rc != _lib.GBPE_OK:
-            raise _lib.GpuBpeError(rc, f"no usable HIP device {self._device} (gbpe_ctx_create status {rc})")
+            why = lib.gbpe_last_error(None).decode("utf-8", "replace")
+            raise _lib.GpuBpeError(rc, f"no context on HIP device {self._device}: {why} (gbpe_ctx_create status {rc})")
         self._ctx = ctx
         mb = C.c_uint64()
         _lib.check(lib.gbpe_ctx_limits(ctx, C.byref(mb)), ctx, "limits")

@@ -203,8 +203,8 @@ napi_value CreateContext(napi_env env, napi_callback_info info) {
     int rc = gbpe_ctx_create(dev, &c->ctx);
     if (rc != GBPE_OK) {
         delete c;
-        std::string m = "No usable HIP device " + std::to_string(dev) + " (gbpe_ctx_create status " +
-                        std::to_string(rc) + ")";
+        std::string m = "No usable HIP device " + std::to_string(dev) + ": " + gbpe_last_error(nullptr) +
+                        " (gbpe_ctx_create status " + std::to_string(rc) + ")";
         napi_throw_error(env, nullptr, m.c_str());
         return nullptr;
     }

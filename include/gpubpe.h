@@ -11,7 +11,8 @@
  * Conventions
  *  - Plain C types only; no HIP or torch types cross the boundary.
  *  - Every function returns an int status (GBPE_OK = 0, negatives = errors);
- *    gbpe_last_error(ctx) returns a message for the last failure on ctx.
+ *    gbpe_last_error(ctx) returns a message for the last failure on ctx
+ *    (ctx NULL: for the last failed gbpe_ctx_create).
  *  - The caller owns every host buffer; buffers are borrowed for the call
  *    and never retained.  The library owns and pools device memory.
  *  - A context is bound to one HIP device and one stream; it is not

@@ -6,7 +6,7 @@ compared with its committed oracle fixture.
     python tools/ab_libs.py gpu-bpe_amd/lib/A/libgpubpe.so gpu-bpe_amd/lib/B/libgpubpe.so:GBPE_X=0 -- en1g c2 code1g
 
 (a library may carry environment settings after a colon, separated by "@", so
-that a GBPE_DEBUG value can hold commas: lib.so:GBPE_DEBUG=zt=4,subk=8@X=1)
+that a GBPE_DEBUG value can hold commas: lib.so:GBPE_DEBUG=zt=4,pair=0@X=1)
 
 Each library runs in its own child process (one .so per process); the runs
 alternate A, B, A, B so drift on the box hits both alike.  AB_TABLE_LOG2 sets
