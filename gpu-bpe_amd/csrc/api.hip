@@ -43,6 +43,9 @@ static const char* const kKernelNames[] = {
     "k_dec_len",              // per-token byte lengths + their block-exclusive scan
     "k_dec_scatter",          // the vocab bytes to their final offsets: k_dec_scatter (16-byte vectors) / k_dec_scatter_plain
     "k_dec_doc_off",          // per-document byte offsets + the check of the token offsets
+    // word-bounded merge-rank encode (gbpe_bpe_encode_words*; the standard pre-tokenise-then-BPE pipeline)
+    "k_me_long",              // arena offsets of the segments above 1024 bytes (both encoders)
+    "k_me_walk_words",        // k_me_walk<true, CS>: segments also cut at word starts, 4096 / 1024 / 256 bytes per lane
 };
 
 // ── context memory pool (common.h GbpePool) ───────────────────────────────
@@ -155,7 +158,7 @@ static int create_err(int code, const std::string& msg) {
 
 extern "C" {
 
-const char* gbpe_version(void) { return "gpubpe 0.8 (gfx950, abi 8)"; }
+const char* gbpe_version(void) { return "gpubpe 0.9 (gfx950, abi 9)"; }
 
 int gbpe_abi_version(void) { return GBPE_ABI_VERSION; }
 

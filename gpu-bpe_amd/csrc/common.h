@@ -55,6 +55,7 @@ struct gbpe_ctx {
     void* pt_agg = nullptr;       uint64_t pt_agg_bytes = 0;   // pre-tokenizer block aggregates
     hipEvent_t ev[8] = {};
     double enc_ms[3] = {0, 0, 0};
+    double bpe_ms[3] = {0, 0, 0};   // word-bounded merge-rank encode: word starts, long + walk, scan + compact
     GbpePool dpool, hpool;   // device / pinned host blocks of trainers and shards
     std::mutex pool_mu;
 };
@@ -146,7 +147,7 @@ __host__ __device__ static inline uint64_t gbpe_div_up(uint64_t a, uint64_t b) {
 // keys); every other tuning value is a compiled default
 constexpr const char* kGbpeDebugKeys[] = {
     "lexicon", "lex_check", "rehash", "delta_mt", "zt", "rfl", "rflz", "lxwg", "lxtwo", "pair", "prej", "poison",
-    "encode_slice", "decode_slice", "dec_plain", "htime", "ptrace", "rtime",
+    "encode_slice", "decode_slice", "dec_plain", "me_cs", "htime", "ptrace", "rtime",
 };
 
 inline long gbpe_debug_knob(const char* key, long def) {
@@ -179,3 +180,5 @@ inline std::string gbpe_debug_unknown() {
 
 // GPT-4 rule word starts of device bytes on ctx->stream (pretok.hip)
 int gbpe_pretok_gpt4_launch(gbpe_ctx* ctx, const uint8_t* d_bytes, uint64_t n, uint8_t* d_ws);
+// heuristic (byte-class) word starts of device bytes on ctx->stream (train.hip); any alignment
+int gbpe_word_boundary_launch(gbpe_ctx* ctx, const uint8_t* d_bytes, uint64_t n, uint8_t* d_ws);

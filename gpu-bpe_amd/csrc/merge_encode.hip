@@ -13,7 +13,7 @@
 // the reference; such merges are dropped on upload, as are repeated pairs
 // (the first rank wins, tokenizer-manager.js:30-33).
 //
-// k_me_walk: one lane per 4096-byte chunk; it owns the segments that START in
+// k_me_walk: one lane per chunk (4096 bytes); it owns the segments that START in
 // its chunk and BPE-encodes each in place (rank lookups in an L2-resident
 // open-addressing table).  Chunk counts → scan.h two-level scan → k_me_compact.
 // A segment longer than ME_LONG bytes (CJK paragraphs, base64, minified code:
@@ -21,6 +21,14 @@
 // applied; it is encoded with a rank-ordered heap over a linked list instead
 // (me_heap: O(len log len), same order: lowest rank first, leftmost first),
 // in an arena k_me_long sized and laid out beforehand.
+//
+// Word-bounded encode (gbpe_bpe_encode_words*): a byte mask of word
+// starts adds cuts, so that the result is the concatenation of each word's own
+// encoding.  k_me_long and k_me_walk take the predicate (WORDS) and the chunk
+// size (CS) as template parameters: <false, ME_CS> is the whole-string encoder,
+// <true, CS> cuts at ws[i] != 0 as well.  Words are a few bytes long, so there a
+// lane's range and not its segments sets the serial length: the word
+// instantiations exist at 4096, 1024 and 256 bytes per lane (GBPE_DEBUG me_cs).
 
 #include "common.h"
 #include "scan.h"
@@ -33,7 +41,10 @@ constexpr int ME_TPB = 64;
 constexpr uint32_t ME_CS = 4096;      // bytes per chunk (a lane's range of segment starts)
 constexpr uint32_t ME_NONE = 0xFFFFFFFFu;
 constexpr uint32_t ME_LONG = 1024;                  // longer segments take the heap path
-constexpr uint32_t ME_LSLOT = ME_CS / ME_LONG + 1;  // long segments that can start in one chunk
+// long segments that can start in one chunk of CS bytes: starts at least ME_LONG + 1 apart,
+// so at most (CS - 1) / (ME_LONG + 1) + 1 <= CS / ME_LONG + 1 of them, under any cut predicate
+constexpr uint32_t me_lslot(uint32_t cs) { return cs / ME_LONG + 1; }
+constexpr uint32_t ME_CS_WORDS = 256;   // shipped chunk size of the word-bounded encode
 constexpr uint32_t ME_DEAD = 0xFFFFFFFFu;
 
 struct MeArena {   // per long segment at offset `off` (bytes of all long segments before it)
@@ -41,7 +52,7 @@ struct MeArena {   // per long segment at offset `off` (bytes of all long segmen
     uint32_t* nxt;
     uint32_t* prv;
     uint64_t* heap;      // [3 off, 3 (off + len)): initial pairs + two per merge
-    const uint64_t* slot;   // per chunk: ME_LSLOT offsets of the long segments starting in it
+    const uint64_t* slot;   // per chunk: me_lslot(CS) offsets of the long segments starting in it
 };
 
 struct MeTable {
@@ -61,26 +72,31 @@ __device__ __forceinline__ uint4 me_find(const MeTable& t, uint32_t pid) {
     return make_uint4(0u, ME_NONE, 0u, 0u);
 }
 
-__device__ __forceinline__ bool me_cut(const uint8_t* __restrict__ in, const MeTable& t, uint64_t i) {
+// a segment starts at byte i: a word start (WORDS), or no merge crosses (i - 1, i)
+template <bool WORDS>
+__device__ __forceinline__ bool me_cut(const uint8_t* __restrict__ in, const uint8_t* __restrict__ ws, const MeTable& t,
+                                       uint64_t i) {
     if (i == 0) return true;
+    if (WORDS && ws[i] != 0) return true;
     const uint32_t k = ((uint32_t)in[i - 1] << 8) | in[i];
     return ((t.cross[k >> 5] >> (k & 31u)) & 1u) == 0u;
 }
 
 // the long segments (> ME_LONG bytes) starting in each chunk: arena offsets
-__global__ __launch_bounds__(ME_TPB) void k_me_long(const uint8_t* __restrict__ in, uint64_t n, MeTable t,
-                                                    unsigned long long* __restrict__ total, uint64_t* __restrict__ slot,
-                                                    uint64_t nchunks) {
+template <bool WORDS, uint32_t CS>
+__global__ __launch_bounds__(ME_TPB) void k_me_long(const uint8_t* __restrict__ in, const uint8_t* __restrict__ ws,
+                                                    uint64_t n, MeTable t, unsigned long long* __restrict__ total,
+                                                    uint64_t* __restrict__ slot, uint64_t nchunks) {
     const uint64_t c = (uint64_t)blockIdx.x * ME_TPB + threadIdx.x;
     if (c >= nchunks) return;
-    const uint64_t lo = c * ME_CS, hi = min(lo + ME_CS, n);
+    const uint64_t lo = c * CS, hi = min(lo + CS, n);
     uint64_t s = lo;
-    while (s < hi && !me_cut(in, t, s)) ++s;
+    while (s < hi && !me_cut<WORDS>(in, ws, t, s)) ++s;
     uint32_t k = 0;
     while (s < hi) {
         uint64_t z = s + 1;
-        while (z < n && !me_cut(in, t, z)) ++z;
-        if (z - s > ME_LONG) slot[c * ME_LSLOT + k++] = atomicAdd(total, (unsigned long long)(z - s));
+        while (z < n && !me_cut<WORDS>(in, ws, t, z)) ++z;
+        if (z - s > ME_LONG) slot[c * me_lslot(CS) + k++] = atomicAdd(total, (unsigned long long)(z - s));
         s = z;
     }
 }
@@ -156,24 +172,26 @@ __device__ uint32_t me_heap(const uint8_t* __restrict__ in, uint32_t len, const 
     return cnt;
 }
 
-__global__ __launch_bounds__(ME_TPB) void k_me_walk(const uint8_t* __restrict__ in, uint64_t n, MeTable t,
-                                                    uint32_t* __restrict__ scratch, uint32_t* __restrict__ counts,
-                                                    uint64_t* __restrict__ base, uint64_t nchunks, MeArena ar) {
+template <bool WORDS, uint32_t CS>
+__global__ __launch_bounds__(ME_TPB) void k_me_walk(const uint8_t* __restrict__ in, const uint8_t* __restrict__ ws,
+                                                    uint64_t n, MeTable t, uint32_t* __restrict__ scratch,
+                                                    uint32_t* __restrict__ counts, uint64_t* __restrict__ base,
+                                                    uint64_t nchunks, MeArena ar) {
     const uint64_t c = (uint64_t)blockIdx.x * ME_TPB + threadIdx.x;
     if (c >= nchunks) return;
-    const uint64_t lo = c * ME_CS, hi = min(lo + ME_CS, n);
+    const uint64_t lo = c * CS, hi = min(lo + CS, n);
     uint64_t s = lo;
-    while (s < hi && !me_cut(in, t, s)) ++s;   // first segment start in the chunk
+    while (s < hi && !me_cut<WORDS>(in, ws, t, s)) ++s;   // first segment start in the chunk
     base[c] = s;
     const uint64_t b0 = s;   // this chunk's tokens go to scratch[b0 ...]: never past the bytes consumed
     uint32_t written = 0, nlong = 0;
     while (s < hi) {
         uint64_t z = s + 1;
-        while (z < n && !me_cut(in, t, z)) ++z;   // the segment [s, z) may run past hi
+        while (z < n && !me_cut<WORDS>(in, ws, t, z)) ++z;   // the segment [s, z) may run past hi
         uint32_t* tok = scratch + b0 + written;
         uint32_t len = (uint32_t)(z - s);
         if (len > ME_LONG) {
-            const uint64_t off = ar.slot[c * ME_LSLOT + nlong++];
+            const uint64_t off = ar.slot[c * me_lslot(CS) + nlong++];
             written += me_heap(in + s, len, t, ar.tok + off, ar.nxt + off, ar.prv + off, ar.heap + 3 * off, tok);
             s = z;
             continue;
@@ -328,14 +346,14 @@ extern "C" int gbpe_bpe_encode(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* bytes
     uint64_t* slot = nullptr;
     unsigned long long* d_long = nullptr;
     unsigned long long long_total = 0;
-    if (e == hipSuccess) e = dev_malloc(ctx, &slot, nchunks * ME_LSLOT * sizeof(uint64_t) + 16);
+    if (e == hipSuccess) e = dev_malloc(ctx, &slot, nchunks * me_lslot(ME_CS) * sizeof(uint64_t) + 16);
     if (e == hipSuccess) {
-        d_long = (unsigned long long*)(slot + nchunks * ME_LSLOT);
+        d_long = (unsigned long long*)(slot + nchunks * me_lslot(ME_CS));
         e = hipMemsetAsync(d_long, 0, 8, s);
     }
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_me_long, dim3((uint32_t)gbpe_div_up(nchunks, ME_TPB)), dim3(ME_TPB), 0, s, d_in, n, t, d_long,
-                           slot, nchunks);
+        hipLaunchKernelGGL((k_me_long<false, ME_CS>), dim3((uint32_t)gbpe_div_up(nchunks, ME_TPB)), dim3(ME_TPB), 0, s,
+                           (const uint8_t*)d_in, (const uint8_t*)nullptr, n, t, d_long, slot, nchunks);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&long_total, d_long, 8, hipMemcpyDeviceToHost, s);
@@ -351,8 +369,8 @@ extern "C" int gbpe_bpe_encode(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* bytes
     }
     ar.slot = slot;
     if (e == hipSuccess)
-        hipLaunchKernelGGL(k_me_walk, dim3((uint32_t)gbpe_div_up(nchunks, ME_TPB)), dim3(ME_TPB), 0, s, d_in, n, t,
-                           scratch, counts, base, nchunks, ar);
+        hipLaunchKernelGGL((k_me_walk<false, ME_CS>), dim3((uint32_t)gbpe_div_up(nchunks, ME_TPB)), dim3(ME_TPB), 0, s,
+                           (const uint8_t*)d_in, (const uint8_t*)nullptr, n, t, scratch, counts, base, nchunks, ar);
     hipLaunchKernelGGL(k_chunk_scan1, dim3((uint32_t)nblk), dim3(SCAN_TPB), 0, s, (const uint32_t*)counts, nchunks,
                        local, blocksum);
     hipLaunchKernelGGL(k_chunk_scan2, dim3(1), dim3(SCAN_TPB), 0, s, blocksum, nblk, total);
@@ -372,5 +390,198 @@ extern "C" int gbpe_bpe_encode(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* bytes
     *n_out = tot;
     if (tot > out_cap) return gbpe_set_error(ctx, GBPE_E_CAPACITY, "bpe encode: output needs %llu tokens",
                                              (unsigned long long)tot);
+    return GBPE_OK;
+}
+
+// ── word-bounded encode, device-resident ──────────────────────
+
+namespace {
+
+template <bool WORDS, uint32_t CS>
+void me_launch_long(hipStream_t s, const uint8_t* in, const uint8_t* ws, uint64_t n, const MeTable& t,
+                    unsigned long long* total, uint64_t* slot, uint64_t nchunks) {
+    hipLaunchKernelGGL((k_me_long<WORDS, CS>), dim3((uint32_t)gbpe_div_up(nchunks, ME_TPB)), dim3(ME_TPB), 0, s, in, ws, n,
+                       t, total, slot, nchunks);
+}
+
+template <bool WORDS, uint32_t CS>
+void me_launch_walk(hipStream_t s, const uint8_t* in, const uint8_t* ws, uint64_t n, const MeTable& t, uint32_t* scratch,
+                    uint32_t* counts, uint64_t* base, uint64_t nchunks, const MeArena& ar) {
+    hipLaunchKernelGGL((k_me_walk<WORDS, CS>), dim3((uint32_t)gbpe_div_up(nchunks, ME_TPB)), dim3(ME_TPB), 0, s, in, ws, n,
+                       t, scratch, counts, base, nchunks, ar);
+}
+
+// the instantiation of a call: no mask at ME_CS, or the word form at cs
+#define ME_DISPATCH(fn, words, cs, ...)                          \
+    do {                                                         \
+        if (!(words)) fn<false, ME_CS>(__VA_ARGS__);             \
+        else if ((cs) == 4096u) fn<true, 4096u>(__VA_ARGS__);    \
+        else if ((cs) == 1024u) fn<true, 1024u>(__VA_ARGS__);    \
+        else fn<true, 256u>(__VA_ARGS__);                        \
+    } while (0)
+
+inline uint64_t up16(uint64_t x) { return (x + 15) & ~15ull; }
+
+// d_in[0, n) (and, mode MASK, d_ws[0, n)) → d_out[0, min(total, out_cap)); n > 0, the mode checked
+int me_words_device(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* d_in, uint64_t n, const uint8_t* d_ws, uint32_t mode,
+                    uint32_t* d_out, uint64_t out_cap, uint64_t* n_out) {
+    hipStream_t s = ctx->stream;
+    const bool words = mode != GBPE_WORDS_NONE;
+    uint32_t cs = ME_CS;
+    if (words) {
+        cs = (uint32_t)gbpe_debug_knob("me_cs", ME_CS_WORDS);   // (read per call: the bench and the tests run all three)
+        if (cs != 4096u && cs != 1024u && cs != 256u)
+            return gbpe_set_error(ctx, GBPE_E_INVALID, "GBPE_DEBUG me_cs: %u is not 4096, 1024 or 256", cs);
+    }
+    const uint32_t lslot = me_lslot(cs);
+    const uint64_t nchunks = gbpe_div_up(n, cs);
+    const uint64_t nblk = gbpe_div_up(nchunks, SCAN_BLK);
+    // one pooled block: scratch tokens (<= 1 per byte), counts, bases, scan state, long-segment slots
+    const uint64_t o_counts = up16(4 * n), o_base = o_counts + up16(4 * nchunks), o_local = o_base + up16(8 * nchunks);
+    const uint64_t o_bsum = o_local + up16(4 * nchunks), o_slot = o_bsum + up16(8 * (nblk + 2));
+    const uint64_t o_long = o_slot + up16(8 * nchunks * lslot);
+    GbpeArray<uint8_t> work, mask, arena;
+    GBPE_HIP(ctx, work.reserve(ctx, o_long + 16));
+    uint32_t* scratch = (uint32_t*)work.p;
+    uint32_t* counts = (uint32_t*)(work.p + o_counts);
+    uint64_t* base = (uint64_t*)(work.p + o_base);
+    uint32_t* local = (uint32_t*)(work.p + o_local);
+    uint64_t* blocksum = (uint64_t*)(work.p + o_bsum);
+    uint64_t* total = blocksum + nblk + 1;
+    uint64_t* slot = (uint64_t*)(work.p + o_slot);
+    unsigned long long* d_long = (unsigned long long*)(work.p + o_long);
+    MeTable t{bp->slots, bp->mask, bp->cross};
+
+    GBPE_HIP(ctx, hipEventRecord(ctx->ev[0], s));
+    if (mode == GBPE_WORDS_HEURISTIC || mode == GBPE_WORDS_GPT4) {
+        GBPE_HIP(ctx, mask.reserve(ctx, n));
+        const int rc = mode == GBPE_WORDS_GPT4 ? gbpe_pretok_gpt4_launch(ctx, d_in, n, mask.p)
+                                               : gbpe_word_boundary_launch(ctx, d_in, n, mask.p);
+        if (rc != GBPE_OK) {
+            hipStreamSynchronize(s);   // (the mask block goes back to the pool)
+            return rc;
+        }
+        d_ws = mask.p;
+    }
+    GBPE_HIP(ctx, hipEventRecord(ctx->ev[1], s));
+    // long segments: their total length sizes the heap arena (none: no arena)
+    hipError_t e = hipMemsetAsync(d_long, 0, 8, s);
+    if (e == hipSuccess) {
+        ME_DISPATCH(me_launch_long, words, cs, s, d_in, d_ws, n, t, d_long, slot, nchunks);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ctx->ev[2], s);
+    if (e == hipSuccess) e = hipMemcpyAsync(ctx->enc_host_total, d_long, 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    uint64_t long_total = 0;
+    memcpy(&long_total, ctx->enc_host_total, 8);
+    MeArena ar{};
+    ar.slot = slot;
+    if (e == hipSuccess && long_total) {
+        e = arena.reserve(ctx, long_total * (3 * sizeof(uint32_t) + 3 * sizeof(uint64_t)) + 64);
+        if (e == hipSuccess) {
+            ar.heap = (uint64_t*)arena.p;
+            ar.tok = (uint32_t*)(ar.heap + 3 * long_total);
+            ar.nxt = ar.tok + long_total;
+            ar.prv = ar.nxt + long_total;
+        }
+    }
+    if (e == hipSuccess) e = hipEventRecord(ctx->ev[3], s);
+    if (e == hipSuccess) {
+        ME_DISPATCH(me_launch_walk, words, cs, s, d_in, d_ws, n, t, scratch, counts, base, nchunks, ar);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ctx->ev[4], s);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_chunk_scan1, dim3((uint32_t)nblk), dim3(SCAN_TPB), 0, s, (const uint32_t*)counts, nchunks,
+                           local, blocksum);
+        hipLaunchKernelGGL(k_chunk_scan2, dim3(1), dim3(SCAN_TPB), 0, s, blocksum, nblk, total);
+        if (out_cap)
+            hipLaunchKernelGGL(k_me_compact, dim3((uint32_t)gbpe_div_up(nchunks, 4)), dim3(256), 0, s,
+                               (const uint32_t*)scratch, (const uint32_t*)counts, (const uint64_t*)base,
+                               (const uint32_t*)local, (const uint64_t*)blocksum, nchunks, d_out, out_cap);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ctx->ev[5], s);
+    if (e == hipSuccess) e = hipMemcpyAsync(ctx->enc_host_total, total, 8, hipMemcpyDeviceToHost, s);
+    const hipError_t es = hipStreamSynchronize(s);   // (always: the pooled blocks are given back on return)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess)
+        return gbpe_set_error(ctx, e == hipErrorOutOfMemory ? GBPE_E_OOM : GBPE_E_DEVICE, "bpe encode (words) failed: %s",
+                              hipGetErrorString(e));
+    float a = 0, b = 0, c = 0, d = 0;
+    hipEventElapsedTime(&a, ctx->ev[0], ctx->ev[1]);
+    hipEventElapsedTime(&b, ctx->ev[1], ctx->ev[2]);
+    hipEventElapsedTime(&c, ctx->ev[3], ctx->ev[4]);
+    hipEventElapsedTime(&d, ctx->ev[4], ctx->ev[5]);
+    ctx->bpe_ms[0] = a;
+    ctx->bpe_ms[1] = (double)b + c;
+    ctx->bpe_ms[2] = d;
+    uint64_t tot = 0;
+    memcpy(&tot, ctx->enc_host_total, 8);
+    *n_out = tot;
+    if (tot > out_cap)
+        return gbpe_set_error(ctx, GBPE_E_CAPACITY, "bpe encode: output needs %llu tokens", (unsigned long long)tot);
+    return GBPE_OK;
+}
+
+int me_words_check(gbpe_ctx* ctx, const void* word_starts, uint32_t mode) {
+    if (mode > GBPE_WORDS_GPT4) return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe encode: unknown words mode %u", mode);
+    if ((word_starts != nullptr) != (mode == GBPE_WORDS_MASK))
+        return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe encode: word_starts goes with GBPE_WORDS_MASK, and only with it");
+    return GBPE_OK;
+}
+
+}  // namespace
+
+extern "C" int gbpe_bpe_encode_words_device(gbpe_ctx* ctx, gbpe_bpe* bp, const void* d_bytes, uint64_t n,
+                                            const void* d_word_starts, uint32_t words_mode, void* d_out, uint64_t out_cap,
+                                            uint64_t* n_out) {
+    if (!ctx || !bp || !n_out || (n && !d_bytes) || (out_cap && !d_out))
+        return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
+    *n_out = 0;
+    const int rc = me_words_check(ctx, d_word_starts, words_mode);
+    if (rc != GBPE_OK) return rc;
+    if ((uintptr_t)d_out & 3u) return gbpe_set_error(ctx, GBPE_E_INVALID, "d_out must be 4-byte aligned");
+    if (n == 0) return GBPE_OK;
+    return me_words_device(ctx, bp, (const uint8_t*)d_bytes, n, (const uint8_t*)d_word_starts, words_mode,
+                           (uint32_t*)d_out, out_cap, n_out);
+}
+
+extern "C" int gbpe_bpe_encode_words(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* bytes, uint64_t n,
+                                     const uint8_t* word_starts, uint32_t words_mode, uint32_t* out, uint64_t out_cap,
+                                     uint64_t* n_out) {
+    if (!ctx || !bp || !n_out || (n && !bytes) || (out_cap && !out))
+        return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
+    *n_out = 0;
+    int rc = me_words_check(ctx, word_starts, words_mode);
+    if (rc != GBPE_OK) return rc;
+    if (n == 0) return GBPE_OK;
+    // one upload of the bytes (and the mask); at most one token per byte comes back
+    const uint64_t cap = out_cap < n ? out_cap : n;
+    const uint64_t o_ws = up16(n), o_out = o_ws + (word_starts ? up16(n) : 0);
+    GbpeArray<uint8_t> io;
+    GBPE_HIP(ctx, io.reserve(ctx, o_out + 4 * cap + 16));
+    hipStream_t s = ctx->stream;
+    uint8_t* d_ws = word_starts ? io.p + o_ws : nullptr;
+    hipError_t e = hipMemcpyAsync(io.p, bytes, n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && word_starts) e = hipMemcpyAsync(d_ws, word_starts, n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+        rc = me_words_device(ctx, bp, io.p, n, d_ws, words_mode, (uint32_t*)(io.p + o_out), cap, n_out);
+        if (rc != GBPE_OK && rc != GBPE_E_CAPACITY) return rc;   // (synchronised there)
+        const uint64_t fit = *n_out < cap ? *n_out : cap;
+        if (fit) e = hipMemcpyAsync(out, io.p + o_out, fit * 4, hipMemcpyDeviceToHost, s);
+    }
+    const hipError_t es = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return gbpe_set_error(ctx, GBPE_E_DEVICE, "bpe encode (words) failed: %s", hipGetErrorString(e));
+    return rc;
+}
+
+extern "C" int gbpe_bpe_encode_last_timing(gbpe_ctx* ctx, double* ms_starts, double* ms_walk, double* ms_compact) {
+    if (!ctx) return GBPE_E_INVALID;
+    if (ms_starts) *ms_starts = ctx->bpe_ms[0];
+    if (ms_walk) *ms_walk = ctx->bpe_ms[1];
+    if (ms_compact) *ms_compact = ctx->bpe_ms[2];
     return GBPE_OK;
 }

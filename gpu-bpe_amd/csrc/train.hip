@@ -771,6 +771,15 @@ extern "C" int gbpe_train(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, const
     return rc;
 }
 
+// device-resident form: d_bytes[n] → d_ws[n] (1 = word start), on the context's stream
+int gbpe_word_boundary_launch(gbpe_ctx* ctx, const uint8_t* d_bytes, uint64_t n, uint8_t* d_ws) {
+    if (n == 0) return GBPE_OK;
+    hipLaunchKernelGGL(k_symbols<uint32_t>, dim3((uint32_t)gbpe_div_up(n, TPB)), dim3(TPB), 0, ctx->stream, d_bytes,
+                       (const uint8_t*)nullptr, (uint32_t*)nullptr, n, d_ws);
+    GBPE_LAUNCH_CHECK(ctx);
+    return GBPE_OK;
+}
+
 extern "C" int gbpe_word_boundary(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, uint8_t* ws_out) {
     if (!ctx || (!bytes && n) || (!ws_out && n)) return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
     if (n == 0) return GBPE_OK;
@@ -779,9 +788,7 @@ extern "C" int gbpe_word_boundary(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t 
     GBPE_HIP(ctx, own.reserve(ctx, 2 * n));
     uint8_t* d = own.p;
     hipError_t e = hipMemcpyAsync(d, bytes, n, hipMemcpyHostToDevice, s);
-    hipLaunchKernelGGL(k_symbols<uint32_t>, dim3((uint32_t)gbpe_div_up(n, TPB)), dim3(TPB), 0, s, d,
-                       (const uint8_t*)nullptr, (uint32_t*)nullptr, n, d + n);
-    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess && gbpe_word_boundary_launch(ctx, d, n, d + n) != GBPE_OK) e = hipErrorLaunchFailure;
     if (e == hipSuccess) e = hipMemcpyAsync(ws_out, d + n, n, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return gbpe_set_error(ctx, GBPE_E_DEVICE, "word boundary failed: %s", hipGetErrorString(e));

@@ -27,6 +27,8 @@ GBPE_TRAIN_SPARSE_EARLY = 1 << 4
 GBPE_TRAIN_TIMING = 1 << 1
 GBPE_TRAIN_GPT4_BOUNDARIES = 1 << 2
 
+GBPE_WORDS_NONE, GBPE_WORDS_MASK, GBPE_WORDS_HEURISTIC, GBPE_WORDS_GPT4 = 0, 1, 2, 3
+
 u8p = C.POINTER(C.c_uint8)
 u32p = C.POINTER(C.c_uint32)
 u64p = C.POINTER(C.c_uint64)
@@ -108,6 +110,12 @@ _SIGS = [
     ("gbpe_bpe_upload", C.c_int, [C.c_void_p, u32p, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("gbpe_bpe_encode", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u32p, C.c_uint64, u64p]),
     ("gbpe_bpe_free", None, [C.c_void_p]),
+    ("gbpe_bpe_encode_words", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, u32p,
+                                        C.c_uint64, u64p]),
+    ("gbpe_bpe_encode_words_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
+                                               C.c_void_p, C.c_uint64, u64p]),
+    ("gbpe_bpe_encode_last_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                              C.POINTER(C.c_double)]),
     ("gbpe_encode_last_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                           C.POINTER(C.c_double)]),
     ("gbpe_vocab_upload", C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_uint32, C.POINTER(C.c_void_p)]),

@@ -559,6 +559,43 @@ napi_value BpeEncode(napi_env env, napi_callback_info info) {
     return make_u32_array(env, out.data(), (size_t)n);
 }
 
+// bpeEncodeWords(ctx, bpe, bytes, wordStarts | null, mode): the merges inside each
+// word alone (gbpe_bpe_encode_words; mode = GBPE_WORDS_*: 1 takes the mask, 2 and 3
+// compute it on the device)
+napi_value BpeEncodeWords(napi_env env, napi_callback_info info) {
+    size_t argc = 5;
+    napi_value argv[5];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Ctx* c = argc >= 1 ? unwrap_external<Ctx>(env, argv[0]) : nullptr;
+    Bpe* b = argc >= 2 ? unwrap_external<Bpe>(env, argv[1]) : nullptr;
+    const uint8_t *data = nullptr, *ws = nullptr;
+    size_t len = 0, ws_len = 0;
+    uint32_t mode = 0;
+    bool ok = ctx_usable(c) && b && b->bpe && argc >= 5 && get_bytes(env, argv[2], &data, &len) &&
+              napi_get_value_uint32(env, argv[4], &mode) == napi_ok;
+    bool has_ws = false;
+    if (ok) {
+        napi_valuetype vt;
+        ok = napi_typeof(env, argv[3], &vt) == napi_ok;
+        has_ws = ok && vt != napi_null && vt != napi_undefined;
+        if (has_ws) ok = get_bytes(env, argv[3], &ws, &ws_len) && ws_len == len;
+    }
+    if (!ok) {
+        napi_throw_type_error(env, nullptr,
+                              "bpeEncodeWords(ctx, bpe, Uint8Array, wordStarts: Uint8Array of the same length | null, mode)");
+        return nullptr;
+    }
+    static const uint8_t kNoByte = 0;
+    if (has_ws && !ws) ws = &kNoByte;   // (an empty mask still goes with mode 1)
+    std::vector<uint32_t> out(len ? len : 1);
+    uint64_t n = 0;
+    std::unique_lock<std::mutex> g(c->mu);
+    int rc = gbpe_bpe_encode_words(c->ctx, b->bpe, data, len, has_ws ? ws : nullptr, mode, out.data(), out.size(), &n);
+    g.unlock();
+    if (rc != GBPE_OK) return throw_status(env, c->ctx, "bpe encode (words)", rc);
+    return make_u32_array(env, out.data(), (size_t)n);
+}
+
 struct EncodeWork {
     napi_async_work work = nullptr;
     napi_deferred deferred = nullptr;
@@ -949,6 +986,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"trieUpload", nullptr, TrieUpload, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"bpeUpload", nullptr, BpeUpload, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"bpeEncode", nullptr, BpeEncode, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"bpeEncodeWords", nullptr, BpeEncodeWords, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"trieFree", nullptr, TrieFree, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"encode", nullptr, Encode, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"encodeBatch", nullptr, EncodeBatch, nullptr, nullptr, nullptr, napi_default, nullptr},

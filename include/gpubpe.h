@@ -29,7 +29,8 @@
 extern "C" {
 #endif
 
-#define GBPE_ABI_VERSION 8   /* 8: device decode (gbpe_vocab_upload, gbpe_decode*, gbpe_decode_batch*);
+#define GBPE_ABI_VERSION 9   /* 9: word-bounded merge-rank encode (gbpe_bpe_encode_words*, gbpe_bpe_encode_last_timing);
+                                 8: device decode (gbpe_vocab_upload, gbpe_decode*, gbpe_decode_batch*);
                                  7: gbpe_encode_batch, gbpe_encode_batch_device (many documents in one call);
                                  6: pair_candidates, pair_rejected added at the end of the stats; 5: paired_merges
                                  added to the stats, gbpe_ctx_trim (round 6); 4: the late-loop stats removed,
@@ -362,6 +363,36 @@ int  gbpe_bpe_upload(gbpe_ctx* ctx, const uint32_t* merges, uint32_t n_merges, g
 int  gbpe_bpe_encode(gbpe_ctx* ctx, gbpe_bpe* bpe, const uint8_t* bytes, uint64_t n, uint32_t* out, uint64_t out_cap,
                      uint64_t* n_out);
 void gbpe_bpe_free(gbpe_bpe* bpe);
+
+/* Merge-rank encode within word boundaries: pre-tokenise, then BPE
+ * inside each word — what a model trained with word starts means.  word_starts is
+ * a byte mask over the input: byte i starts a word iff word_starts[i] != 0, and
+ * byte 0 always does.  The output is the concatenation, over the words in order,
+ * of what gbpe_bpe_encode returns for that word's bytes alone; no token spans a
+ * word start.  Where the word starts come from: */
+#define GBPE_WORDS_NONE       0u   /* no word cuts: gbpe_bpe_encode's result */
+#define GBPE_WORDS_MASK       1u   /* the caller's mask */
+#define GBPE_WORDS_HEURISTIC  2u   /* gbpe_word_boundary's mask of the same bytes, computed on the device */
+#define GBPE_WORDS_GPT4       3u   /* gbpe_pretokenize_gpt4's mask of the same bytes (its domain), on the device */
+/* word_starts is non-NULL exactly when words_mode is GBPE_WORDS_MASK; anything
+ * else, and an unknown mode, is GBPE_E_INVALID with nothing launched.  n == 0:
+ * GBPE_OK, *n_out = 0, nothing launched.  On GBPE_E_CAPACITY *n_out holds the
+ * required token count, the first out_cap tokens are in place and nothing is
+ * written at or beyond out[out_cap]; out == NULL with out_cap == 0 asks for the
+ * size.  The input limit is gbpe_bpe_encode's (one device allocation). */
+int gbpe_bpe_encode_words(gbpe_ctx* ctx, gbpe_bpe* bpe, const uint8_t* bytes, uint64_t n, const uint8_t* word_starts,
+                          uint32_t words_mode, uint32_t* out, uint64_t out_cap, uint64_t* n_out);
+/* Device-resident variant, on the context's stream: d_bytes and d_word_starts are
+ * device pointers of any alignment, d_out (u32) is 4-byte aligned, else
+ * GBPE_E_INVALID.  Only d_bytes[0, n) and d_word_starts[0, n) are read and only
+ * d_out[0, min(total, out_cap)) is written.  Work buffers come from the context's
+ * pool. */
+int gbpe_bpe_encode_words_device(gbpe_ctx* ctx, gbpe_bpe* bpe, const void* d_bytes, uint64_t n,
+                                 const void* d_word_starts, uint32_t words_mode, void* d_out, uint64_t out_cap,
+                                 uint64_t* n_out);
+/* device ms of the last word encode's kernels: the word-start kernels, k_me_long
+ * plus the walk, the count scan plus the compaction */
+int gbpe_bpe_encode_last_timing(gbpe_ctx* ctx, double* ms_starts, double* ms_walk, double* ms_compact);
 
 /* device ms of the last encode's kernels (walk, scan, compact); after a batch call:
  * the walk, every scan and table kernel (document table, descriptors, count scan),
