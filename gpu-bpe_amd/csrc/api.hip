@@ -46,6 +46,12 @@ static const char* const kKernelNames[] = {
     // word-bounded merge-rank encode (gbpe_bpe_encode_words*; the standard pre-tokenise-then-BPE pipeline)
     "k_me_long",              // arena offsets of the segments above 1024 bytes (both encoders)
     "k_me_walk_words",        // k_me_walk<true, CS>: segments also cut at word starts, 4096 / 1024 / 256 bytes per lane
+    // the same for many documents in one call (gbpe_pretokenize_gpt4_batch*, gbpe_bpe_encode_words_batch*)
+    "k_doc_flags",            // document offsets checked + a flag per document start
+    "k_pretok_docs",          // k_pt_scan1_docs / k_pt_mark_docs: the GPT-4 rules bounded by the document flags
+    "k_me_mask01",            // the caller's mask as 0 / 1 (bit 1 of a mask byte marks a document start)
+    "k_me_walk_docs",         // k_me_walk_docs<CS>: the word walk + tokens written before each document start
+    "k_me_tok_off",           // per-document token offsets
 };
 
 // ── context memory pool (common.h GbpePool) ───────────────────────────────
@@ -158,7 +164,7 @@ static int create_err(int code, const std::string& msg) {
 
 extern "C" {
 
-const char* gbpe_version(void) { return "gpubpe 0.9 (gfx950, abi 9)"; }
+const char* gbpe_version(void) { return "gpubpe 0.10 (gfx950, abi 10)"; }
 
 int gbpe_abi_version(void) { return GBPE_ABI_VERSION; }
 

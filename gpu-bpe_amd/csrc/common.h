@@ -180,5 +180,15 @@ inline std::string gbpe_debug_unknown() {
 
 // GPT-4 rule word starts of device bytes on ctx->stream (pretok.hip)
 int gbpe_pretok_gpt4_launch(gbpe_ctx* ctx, const uint8_t* d_bytes, uint64_t n, uint8_t* d_ws);
+// the same for many documents in one buffer: d_flags[n] (4-byte aligned) is non-zero where a document starts
+int gbpe_pretok_gpt4_docs_launch(gbpe_ctx* ctx, const uint8_t* d_bytes, uint64_t n, const uint8_t* d_flags, uint8_t* d_ws);
+// Document offsets of the batch calls (doc_off[n_docs + 1], from 0 to n, non-decreasing).
+// k_doc_flags (pretok.hip), one lane per document: ORs what is wrong into *d_invalid
+// (nullptr: unchecked) and `bit` into d_flags[doc_off[d]] (nullptr: no flags) for doc_off[d] < n.
+constexpr uint32_t GBPE_DOC_BAD_ORDER = 1u, GBPE_DOC_BAD_FIRST = 2u, GBPE_DOC_BAD_LAST = 4u;
+int gbpe_doc_flags_launch(gbpe_ctx* ctx, const uint64_t* d_doc_off, uint64_t n_docs, uint64_t n, uint8_t* d_flags,
+                          uint32_t bit, uint32_t* d_invalid);
+int gbpe_doc_offsets_check(gbpe_ctx* ctx, const char* what, const uint64_t* doc_off, uint64_t n_docs, uint64_t n);   // host
+int gbpe_doc_offsets_error(gbpe_ctx* ctx, const char* what, uint32_t bad);
 // heuristic (byte-class) word starts of device bytes on ctx->stream (train.hip); any alignment
 int gbpe_word_boundary_launch(gbpe_ctx* ctx, const uint8_t* d_bytes, uint64_t n, uint8_t* d_ws);

@@ -29,6 +29,11 @@
 // <true, CS> cuts at ws[i] != 0 as well.  Words are a few bytes long, so there a
 // lane's range and not its segments sets the serial length: the word
 // instantiations exist at 4096, 1024 and 256 bytes per lane (GBPE_DEBUG me_cs).
+//
+// Many documents in one call (gbpe_bpe_encode_words_batch*): a document
+// start is one more cut, so the tokens are the word walk's under the mask `the mode's
+// per-document mask | document starts`; k_me_walk_docs also notes how many tokens its
+// lane had written at each document start, and k_me_tok_off adds the chunk's prefix.
 
 #include "common.h"
 #include "scan.h"
@@ -220,6 +225,113 @@ __global__ __launch_bounds__(ME_TPB) void k_me_walk(const uint8_t* __restrict__ 
         s = z;
     }
     counts[c] = written;
+}
+
+// the first document whose offset is p (p is one of doc_off[0, n_docs))
+__device__ __forceinline__ uint64_t me_first_doc(const uint64_t* __restrict__ doc_off, uint64_t n_docs, uint64_t p) {
+    uint64_t lo = 0, hi = n_docs;
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (doc_off[mid] < p) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// Per-document token offsets of the batch call: bit 1 of a mask byte
+// says a document starts there.  A document start is a segment start of the chunk that
+// holds it, so its first token is that chunk's scanned prefix plus what the chunk's lane
+// had written when it got there: doc_written[first document at that offset].
+struct MeDocs {
+    const uint64_t* doc_off;
+    uint64_t n_docs;
+    uint32_t* written;
+};
+constexpr uint32_t ME_DOC_BIT = 2u;
+
+// k_me_walk<true, CS> + the tokens written before each document start
+template <uint32_t CS>
+__global__ __launch_bounds__(ME_TPB) void k_me_walk_docs(const uint8_t* __restrict__ in, const uint8_t* __restrict__ ws,
+                                                         uint64_t n, MeTable t, uint32_t* __restrict__ scratch,
+                                                         uint32_t* __restrict__ counts, uint64_t* __restrict__ base,
+                                                         uint64_t nchunks, MeArena ar, MeDocs docs) {
+    const uint64_t c = (uint64_t)blockIdx.x * ME_TPB + threadIdx.x;
+    if (c >= nchunks) return;
+    const uint64_t lo = c * CS, hi = min(lo + CS, n);
+    uint64_t s = lo;
+    while (s < hi && !me_cut<true>(in, ws, t, s)) ++s;   // first segment start in the chunk
+    base[c] = s;
+    const uint64_t b0 = s;   // this chunk's tokens go to scratch[b0 ...]: never past the bytes consumed
+    uint32_t written = 0, nlong = 0;
+    while (s < hi) {
+        uint64_t z = s + 1;
+        while (z < n && !me_cut<true>(in, ws, t, z)) ++z;   // the segment [s, z) may run past hi
+        if (ws[s] & ME_DOC_BIT) docs.written[me_first_doc(docs.doc_off, docs.n_docs, s)] = written;
+        uint32_t* tok = scratch + b0 + written;
+        uint32_t len = (uint32_t)(z - s);
+        if (len > ME_LONG) {
+            const uint64_t off = ar.slot[c * me_lslot(CS) + nlong++];
+            written += me_heap(in + s, len, t, ar.tok + off, ar.nxt + off, ar.prv + off, ar.heap + 3 * off, tok);
+            s = z;
+            continue;
+        }
+        for (uint32_t j = 0; j < len; ++j) tok[j] = in[s + j];
+        while (len >= 2) {
+            uint32_t best = ME_NONE, bpid = 0, bnew = 0;
+            for (uint32_t j = 0; j + 1 < len; ++j) {
+                const uint32_t pid = (tok[j] << 16) | tok[j + 1];
+                const uint4 e = me_find(t, pid);
+                if (e.y < best) { best = e.y; bpid = pid; bnew = e.z; }
+            }
+            if (best == ME_NONE) break;
+            uint32_t w = 0, j = 0;   // this rank, every occurrence, left to right
+            while (j < len) {
+                if (j + 1 < len && ((tok[j] << 16) | tok[j + 1]) == bpid) {
+                    tok[w++] = bnew;
+                    j += 2;
+                } else {
+                    tok[w++] = tok[j++];
+                }
+            }
+            len = w;
+        }
+        written += len;
+        s = z;
+    }
+    counts[c] = written;
+}
+
+// the caller's mask as 0 / 1 (any alignment), four bytes per lane: bit 1 stays free for the document starts
+__global__ __launch_bounds__(256) void k_me_mask01(const uint8_t* __restrict__ ws, uint64_t n, uint8_t* __restrict__ m) {
+    const uint64_t i = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    if (i + 4 <= n) {
+        uint32_t v = 0;
+        for (int k = 0; k < 4; ++k) v |= (ws[i + k] != 0 ? 1u : 0u) << (8 * k);
+        *reinterpret_cast<uint32_t*>(m + i) = v;   // (m is a pooled block: aligned)
+    } else {
+        for (uint64_t j = i; j < n; ++j) m[j] = ws[j] != 0;
+    }
+}
+
+// one lane per document and one for the closing entry: a document that starts inside the
+// bytes begins at its chunk's prefix + what the walk stored for the first document at its
+// offset (empty documents share it); one that starts at n begins at the total
+__global__ __launch_bounds__(256) void k_me_tok_off(const uint64_t* __restrict__ doc_off, uint64_t n_docs, uint64_t n,
+                                                    uint32_t cs, const uint32_t* __restrict__ doc_written,
+                                                    const uint32_t* __restrict__ local,
+                                                    const uint64_t* __restrict__ blocksum,
+                                                    const uint64_t* __restrict__ total, uint64_t* __restrict__ tok_off) {
+    const uint64_t d = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (d > n_docs) return;
+    const uint64_t p = d < n_docs ? doc_off[d] : n;
+    if (p >= n) {
+        tok_off[d] = *total;
+        return;
+    }
+    const uint64_t d0 = (d == 0 || doc_off[d - 1] < p) ? d : me_first_doc(doc_off, n_docs, p);
+    const uint64_t c = p / cs;
+    tok_off[d] = blocksum[c / SCAN_BLK] + local[c] + doc_written[d0];
 }
 
 __global__ __launch_bounds__(256) void k_me_compact(const uint32_t* __restrict__ scratch,
@@ -575,6 +687,211 @@ extern "C" int gbpe_bpe_encode_words(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t*
     const hipError_t es = hipStreamSynchronize(s);
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return gbpe_set_error(ctx, GBPE_E_DEVICE, "bpe encode (words) failed: %s", hipGetErrorString(e));
+    return rc;
+}
+
+// ── many documents in one call (gbpe_bpe_encode_words_batch*) ──
+
+namespace {
+
+template <uint32_t CS>
+void me_launch_walk_docs(hipStream_t s, const uint8_t* in, const uint8_t* ws, uint64_t n, const MeTable& t,
+                         uint32_t* scratch, uint32_t* counts, uint64_t* base, uint64_t nchunks, const MeArena& ar,
+                         const MeDocs& docs) {
+    hipLaunchKernelGGL((k_me_walk_docs<CS>), dim3((uint32_t)gbpe_div_up(nchunks, ME_TPB)), dim3(ME_TPB), 0, s, in, ws, n, t,
+                       scratch, counts, base, nchunks, ar, docs);
+}
+
+// d_in[0, n), d_doc_off[0, n_docs] (and, mode MASK, d_ws[0, n)) → d_out[0, min(total, out_cap)) and
+// d_tok_off[0, n_docs]; n, n_docs > 0, the mode checked.  The tokens are the word kernels' under the
+// mask `the mode's per-document mask | document starts` (mode NONE: document starts only).  The
+// offsets are checked by the first kernel; what it found comes back with the long-segment total, the
+// call's first synchronise, before anything is written to d_out or d_tok_off.
+int me_words_batch_device(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* d_in, uint64_t n, const uint64_t* d_doc_off,
+                          uint64_t n_docs, const uint8_t* d_ws, uint32_t mode, uint32_t* d_out, uint64_t out_cap,
+                          uint64_t* d_tok_off, uint64_t* n_out) {
+    hipStream_t s = ctx->stream;
+    const uint32_t cs = (uint32_t)gbpe_debug_knob("me_cs", ME_CS_WORDS);
+    if (cs != 4096u && cs != 1024u && cs != 256u)
+        return gbpe_set_error(ctx, GBPE_E_INVALID, "GBPE_DEBUG me_cs: %u is not 4096, 1024 or 256", cs);
+    const uint32_t lslot = me_lslot(cs);
+    const uint64_t nchunks = gbpe_div_up(n, cs);
+    const uint64_t nblk = gbpe_div_up(nchunks, SCAN_BLK);
+    // one pooled block: me_words_device's, then the per-document counts, the mask and (GPT-4) the flags
+    const uint64_t o_counts = up16(4 * n), o_base = o_counts + up16(4 * nchunks), o_local = o_base + up16(8 * nchunks);
+    const uint64_t o_bsum = o_local + up16(4 * nchunks), o_slot = o_bsum + up16(8 * (nblk + 2));
+    const uint64_t o_long = o_slot + up16(8 * nchunks * lslot), o_docw = o_long + 16, o_mask = o_docw + up16(4 * n_docs);
+    const uint64_t o_flags = o_mask + up16(n), o_end = o_flags + (mode == GBPE_WORDS_GPT4 ? up16(n) : 0);
+    GbpeArray<uint8_t> work, arena;
+    GBPE_HIP(ctx, work.reserve(ctx, o_end + 16));
+    uint32_t* scratch = (uint32_t*)work.p;
+    uint32_t* counts = (uint32_t*)(work.p + o_counts);
+    uint64_t* base = (uint64_t*)(work.p + o_base);
+    uint32_t* local = (uint32_t*)(work.p + o_local);
+    uint64_t* blocksum = (uint64_t*)(work.p + o_bsum);
+    uint64_t* total = blocksum + nblk + 1;
+    uint64_t* slot = (uint64_t*)(work.p + o_slot);
+    unsigned long long* d_long = (unsigned long long*)(work.p + o_long);
+    uint32_t* d_invalid = (uint32_t*)(work.p + o_long + 8);
+    uint32_t* doc_written = (uint32_t*)(work.p + o_docw);
+    uint8_t* m = work.p + o_mask;
+    uint8_t* flags = work.p + o_flags;
+    MeTable t{bp->slots, bp->mask, bp->cross};
+
+    GBPE_HIP(ctx, hipEventRecord(ctx->ev[0], s));
+    GBPE_HIP(ctx, hipMemsetAsync(d_long, 0, 16, s));
+    int rc = GBPE_OK;
+    if (mode == GBPE_WORDS_GPT4) {
+        GBPE_HIP(ctx, hipMemsetAsync(flags, 0, n, s));
+        rc = gbpe_doc_flags_launch(ctx, d_doc_off, n_docs, n, flags, 1u, d_invalid);
+        if (rc == GBPE_OK) rc = gbpe_pretok_gpt4_docs_launch(ctx, d_in, n, flags, m);
+        if (rc == GBPE_OK) rc = gbpe_doc_flags_launch(ctx, d_doc_off, n_docs, n, m, ME_DOC_BIT, nullptr);
+    } else {
+        rc = gbpe_doc_flags_launch(ctx, d_doc_off, n_docs, n, nullptr, 0u, d_invalid);
+        if (rc == GBPE_OK && mode == GBPE_WORDS_NONE) {
+            GBPE_HIP(ctx, hipMemsetAsync(m, 0, n, s));
+        } else if (rc == GBPE_OK && mode == GBPE_WORDS_MASK) {
+            hipLaunchKernelGGL(k_me_mask01, dim3((uint32_t)gbpe_div_up(n, 1024)), dim3(256), 0, s, d_ws, n, m);
+        } else if (rc == GBPE_OK) {
+            rc = gbpe_word_boundary_launch(ctx, d_in, n, m);
+        }
+        if (rc == GBPE_OK) rc = gbpe_doc_flags_launch(ctx, d_doc_off, n_docs, n, m, ME_DOC_BIT, nullptr);
+    }
+    if (rc != GBPE_OK) {
+        hipStreamSynchronize(s);   // (the work block goes back to the pool)
+        return rc;
+    }
+    GBPE_HIP(ctx, hipEventRecord(ctx->ev[1], s));
+    // long segments: their total length sizes the heap arena (none: no arena)
+    ME_DISPATCH(me_launch_long, true, cs, s, d_in, (const uint8_t*)m, n, t, d_long, slot, nchunks);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(ctx->ev[2], s);
+    if (e == hipSuccess) e = hipMemcpyAsync(ctx->enc_host_total, d_long, 16, hipMemcpyDeviceToHost, s);
+    const hipError_t e1 = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = e1;
+    uint64_t long_total = 0;
+    uint32_t bad = 0;
+    memcpy(&long_total, ctx->enc_host_total, 8);
+    memcpy(&bad, (const uint8_t*)ctx->enc_host_total + 8, 4);
+    if (e == hipSuccess && bad) return gbpe_doc_offsets_error(ctx, "bpe encode batch", bad);   // nothing was written
+    MeArena ar{};
+    ar.slot = slot;
+    if (e == hipSuccess && long_total) {
+        e = arena.reserve(ctx, long_total * (3 * sizeof(uint32_t) + 3 * sizeof(uint64_t)) + 64);
+        if (e == hipSuccess) {
+            ar.heap = (uint64_t*)arena.p;
+            ar.tok = (uint32_t*)(ar.heap + 3 * long_total);
+            ar.nxt = ar.tok + long_total;
+            ar.prv = ar.nxt + long_total;
+        }
+    }
+    if (e == hipSuccess) e = hipEventRecord(ctx->ev[3], s);
+    if (e == hipSuccess) {
+        const MeDocs docs{d_doc_off, n_docs, doc_written};
+        if (cs == 4096u) me_launch_walk_docs<4096u>(s, d_in, m, n, t, scratch, counts, base, nchunks, ar, docs);
+        else if (cs == 1024u) me_launch_walk_docs<1024u>(s, d_in, m, n, t, scratch, counts, base, nchunks, ar, docs);
+        else me_launch_walk_docs<256u>(s, d_in, m, n, t, scratch, counts, base, nchunks, ar, docs);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ctx->ev[4], s);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_chunk_scan1, dim3((uint32_t)nblk), dim3(SCAN_TPB), 0, s, (const uint32_t*)counts, nchunks,
+                           local, blocksum);
+        hipLaunchKernelGGL(k_chunk_scan2, dim3(1), dim3(SCAN_TPB), 0, s, blocksum, nblk, total);
+        if (out_cap)
+            hipLaunchKernelGGL(k_me_compact, dim3((uint32_t)gbpe_div_up(nchunks, 4)), dim3(256), 0, s,
+                               (const uint32_t*)scratch, (const uint32_t*)counts, (const uint64_t*)base,
+                               (const uint32_t*)local, (const uint64_t*)blocksum, nchunks, d_out, out_cap);
+        // (runs whether or not the tokens fit: tok_off is complete on GBPE_E_CAPACITY)
+        hipLaunchKernelGGL(k_me_tok_off, dim3((uint32_t)gbpe_div_up(n_docs + 1, 256)), dim3(256), 0, s, d_doc_off, n_docs, n,
+                           cs, (const uint32_t*)doc_written, (const uint32_t*)local, (const uint64_t*)blocksum,
+                           (const uint64_t*)total, d_tok_off);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ctx->ev[5], s);
+    if (e == hipSuccess) e = hipMemcpyAsync(ctx->enc_host_total, total, 8, hipMemcpyDeviceToHost, s);
+    const hipError_t es = hipStreamSynchronize(s);   // (always: the pooled blocks are given back on return)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess)
+        return gbpe_set_error(ctx, e == hipErrorOutOfMemory ? GBPE_E_OOM : GBPE_E_DEVICE, "bpe encode batch failed: %s",
+                              hipGetErrorString(e));
+    float a = 0, b = 0, c = 0, d = 0;
+    hipEventElapsedTime(&a, ctx->ev[0], ctx->ev[1]);
+    hipEventElapsedTime(&b, ctx->ev[1], ctx->ev[2]);
+    hipEventElapsedTime(&c, ctx->ev[3], ctx->ev[4]);
+    hipEventElapsedTime(&d, ctx->ev[4], ctx->ev[5]);
+    ctx->bpe_ms[0] = a;
+    ctx->bpe_ms[1] = (double)b + c;
+    ctx->bpe_ms[2] = d;
+    uint64_t tot = 0;
+    memcpy(&tot, ctx->enc_host_total, 8);
+    *n_out = tot;
+    if (tot > out_cap)
+        return gbpe_set_error(ctx, GBPE_E_CAPACITY, "bpe encode batch: output needs %llu tokens", (unsigned long long)tot);
+    return GBPE_OK;
+}
+
+}  // namespace
+
+extern "C" int gbpe_bpe_encode_words_batch_device(gbpe_ctx* ctx, gbpe_bpe* bp, const void* d_bytes, uint64_t n,
+                                                  const void* d_doc_off, uint64_t n_docs, const void* d_word_starts,
+                                                  uint32_t words_mode, void* d_out, uint64_t out_cap, void* d_tok_off,
+                                                  uint64_t* n_out) {
+    if (!ctx || !bp || !n_out || !d_tok_off || (n_docs && !d_doc_off) || (n && n_docs && !d_bytes) || (out_cap && !d_out))
+        return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
+    *n_out = 0;
+    const int rc = me_words_check(ctx, d_word_starts, words_mode);
+    if (rc != GBPE_OK) return rc;
+    if ((uintptr_t)d_out & 3u) return gbpe_set_error(ctx, GBPE_E_INVALID, "d_out must be 4-byte aligned");
+    if (((uintptr_t)d_doc_off | (uintptr_t)d_tok_off) & 7u)
+        return gbpe_set_error(ctx, GBPE_E_INVALID, "d_doc_off and d_tok_off must be 8-byte aligned");
+    if (n == 0 || n_docs == 0) {
+        GBPE_HIP(ctx, hipMemsetAsync(d_tok_off, 0, (n_docs + 1) * 8, ctx->stream));
+        GBPE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return GBPE_OK;
+    }
+    return me_words_batch_device(ctx, bp, (const uint8_t*)d_bytes, n, (const uint64_t*)d_doc_off, n_docs,
+                                 (const uint8_t*)d_word_starts, words_mode, (uint32_t*)d_out, out_cap, (uint64_t*)d_tok_off,
+                                 n_out);
+}
+
+extern "C" int gbpe_bpe_encode_words_batch(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* bytes, uint64_t n,
+                                           const uint64_t* doc_off, uint64_t n_docs, const uint8_t* word_starts,
+                                           uint32_t words_mode, uint32_t* out, uint64_t out_cap, uint64_t* tok_off,
+                                           uint64_t* n_out) {
+    if (!ctx || !bp || !n_out || !tok_off || (n_docs && !doc_off) || (n && n_docs && !bytes) || (out_cap && !out))
+        return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
+    *n_out = 0;
+    int rc = me_words_check(ctx, word_starts, words_mode);
+    if (rc != GBPE_OK) return rc;
+    if (n == 0 || n_docs == 0) {
+        for (uint64_t d = 0; d <= n_docs; ++d) tok_off[d] = 0;
+        return GBPE_OK;
+    }
+    rc = gbpe_doc_offsets_check(ctx, "bpe encode batch", doc_off, n_docs, n);   // before anything is launched
+    if (rc != GBPE_OK) return rc;
+    // one upload of the offsets, the bytes (and the mask); at most one token per byte comes back
+    const uint64_t cap = out_cap < n ? out_cap : n;
+    const uint64_t o_tok = up16(8 * (n_docs + 1)), o_in = 2 * o_tok, o_ws = o_in + up16(n);
+    const uint64_t o_out = o_ws + (word_starts ? up16(n) : 0);
+    GbpeArray<uint8_t> io;
+    GBPE_HIP(ctx, io.reserve(ctx, o_out + 4 * cap + 16));
+    hipStream_t s = ctx->stream;
+    uint8_t* d_ws = word_starts ? io.p + o_ws : nullptr;
+    hipError_t e = hipMemcpyAsync(io.p, doc_off, 8 * (n_docs + 1), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(io.p + o_in, bytes, n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && word_starts) e = hipMemcpyAsync(d_ws, word_starts, n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+        rc = me_words_batch_device(ctx, bp, io.p + o_in, n, (const uint64_t*)io.p, n_docs, d_ws, words_mode,
+                                   (uint32_t*)(io.p + o_out), cap, (uint64_t*)(io.p + o_tok), n_out);
+        if (rc != GBPE_OK && rc != GBPE_E_CAPACITY) return rc;   // (synchronised there)
+        e = hipMemcpyAsync(tok_off, io.p + o_tok, 8 * (n_docs + 1), hipMemcpyDeviceToHost, s);
+        const uint64_t fit = *n_out < cap ? *n_out : cap;
+        if (e == hipSuccess && fit) e = hipMemcpyAsync(out, io.p + o_out, fit * 4, hipMemcpyDeviceToHost, s);
+    }
+    const hipError_t es = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return gbpe_set_error(ctx, GBPE_E_DEVICE, "bpe encode batch failed: %s", hipGetErrorString(e));
     return rc;
 }
 

@@ -114,6 +114,10 @@ _SIGS = [
                                         C.c_uint64, u64p]),
     ("gbpe_bpe_encode_words_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
                                                C.c_void_p, C.c_uint64, u64p]),
+    ("gbpe_bpe_encode_words_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_uint64, C.c_void_p,
+                                              C.c_uint32, u32p, C.c_uint64, u64p, u64p]),
+    ("gbpe_bpe_encode_words_batch_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                     C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, u64p]),
     ("gbpe_bpe_encode_last_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                               C.POINTER(C.c_double)]),
     ("gbpe_encode_last_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -136,6 +140,9 @@ _SIGS = [
     ("gbpe_synchronize", C.c_int, [C.c_void_p]),
     ("gbpe_pretokenize_gpt4", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     ("gbpe_pretokenize_gpt4_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    ("gbpe_pretokenize_gpt4_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_uint64, C.c_void_p]),
+    ("gbpe_pretokenize_gpt4_batch_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                     C.c_void_p]),
     ("gbpe_ctx_set_stream", C.c_int, [C.c_void_p, C.c_void_p]),
     ("gbpe_ctx_get_stream", C.c_void_p, [C.c_void_p]),
     ("gbpe_trainer_export_state", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_uint64, u64p,

@@ -1,7 +1,8 @@
 """MergeEncoder — TokenizerManager.encode (src/bpe/tokenizer/tokenizer-manager.js:13-61)
 on the device: the learned merges applied in rank order to the whole byte
 string, through gbpe_bpe_upload / gbpe_bpe_encode — or, with word starts, inside
-each word alone (gbpe_bpe_encode_words: pre-tokenise, then BPE per word)."""
+each word alone (gbpe_bpe_encode_words: pre-tokenise, then BPE per word); many
+documents in one call through gbpe_bpe_encode_words_batch."""
 from __future__ import annotations
 
 import ctypes as C
@@ -79,6 +80,32 @@ class MergeEncoder:
                                                  out.ctypes.data_as(_lib.u32p), out.shape[0], C.byref(n)),
                        ctx, "bpe encode (words)")
         return out[: n.value].copy()
+
+    def encode_batch(self, docs, offsets=None, word_starts=None, words=None):
+        """Many documents in one call (gbpe_bpe_encode_words_batch): returns
+        ``(tokens, offsets)``, document d's tokens being
+        ``tokens[offsets[d]:offsets[d + 1]]`` — exactly ``encode_bytes`` of that
+        document alone in the same mode.  ``docs`` and ``offsets`` are
+        ``flatten_documents``'s; ``word_starts`` is one mask over the
+        concatenation (a document's first byte starts a word whatever it says)."""
+        from .tokenizer import flatten_documents
+        buf, offs = flatten_documents(docs, offsets)
+        n, n_docs = int(buf.shape[0]), int(offs.shape[0]) - 1
+        mode, mask = checked_word_starts(n, word_starts, words)
+        lib = _lib.load()
+        ctx = self._engine.device
+        out = np.empty(max(1, n), dtype=np.uint32)
+        tok_off = np.zeros(n_docs + 1, dtype=np.uint64)
+        cnt = C.c_uint64()
+        if mask is not None and not n:
+            mask = np.zeros(1, dtype=np.uint8)   # (a non-NULL pointer goes with the mode)
+        _lib.check(lib.gbpe_bpe_encode_words_batch(ctx, self._h, buf.ctypes.data_as(C.c_void_p), n,
+                                                   offs.ctypes.data_as(_lib.u64p), n_docs,
+                                                   mask.ctypes.data_as(C.c_void_p) if mask is not None else None, mode,
+                                                   out.ctypes.data_as(_lib.u32p), out.shape[0],
+                                                   tok_off.ctypes.data_as(_lib.u64p), C.byref(cnt)),
+                   ctx, "bpe encode batch")
+        return out[: cnt.value].copy(), tok_off
 
     def encode(self, text, word_starts=None, words=None) -> dict:
         """{tokens, text} like TokenizerManager.encode's result (tokenizer-manager.js:60)."""

@@ -32,9 +32,27 @@ class GpuPreTokenizer:
                        "pretokenize")
         return {"bytes": data, "wordStarts": ws}
 
+    def pre_tokenize_batch(self, docs, offsets=None):
+        """Word starts of many documents in one call (gbpe_pretokenize_gpt4_batch):
+        returns ``(mask, offsets)`` over the concatenation, the mask of document d
+        being ``mask[offsets[d]:offsets[d + 1]]`` — exactly ``pre_tokenize_bytes``
+        of that document alone.  ``docs`` and ``offsets`` are ``flatten_documents``'s.
+        The mask is the ``word_starts`` a trainer takes for the concatenation."""
+        from .tokenizer import flatten_documents
+        buf, offs = flatten_documents(docs, offsets)
+        n, n_docs = int(buf.shape[0]), int(offs.shape[0]) - 1
+        ws = np.zeros(n, dtype=np.uint8)
+        if n and n_docs:
+            ctx = self._engine.device
+            _lib.check(_lib.load().gbpe_pretokenize_gpt4_batch(ctx, buf.ctypes.data_as(C.c_void_p), n,
+                                                               offs.ctypes.data_as(_lib.u64p), n_docs,
+                                                               ws.ctypes.data_as(C.c_void_p)), ctx, "pretokenize batch")
+        return ws, offs
+
     def pre_tokenize(self, text: str) -> dict:
         return self.pre_tokenize_bytes(text.encode("utf-8"))
 
     # reference spelling
     preTokenizeBytes = pre_tokenize_bytes
     preTokenize = pre_tokenize
+    preTokenizeBatch = pre_tokenize_batch

@@ -17,6 +17,8 @@
 //   trieUpload(ctx, nodes: Uint32Array, edges: Uint32Array) -> trie      trieFree(trie)
 //   encode(ctx, trie, bytes, chunkSize) -> Promise<Uint32Array>
 //   encodeBatch(ctx, trie, bytes, offsets: Float64Array, chunkSize) -> Promise<{tokens: Uint32Array, offsets: Float64Array}>
+//   bpeEncodeWordsBatch(ctx, bpe, bytes, offsets: Float64Array, wordStarts | null, mode) -> {tokens: Uint32Array, offsets: Float64Array}
+//   pretokenizeGpt4Batch(ctx, bytes, offsets: Float64Array) -> Uint8Array
 //   vocabUpload(ctx, bytes: Uint8Array, offsets: Float64Array) -> vocab   vocabFree(vocab)
 //   decode(ctx, vocab, tokens: Uint32Array) -> Promise<Uint8Array>
 //   decodeBatch(ctx, vocab, tokens: Uint32Array, offsets: Float64Array) -> Promise<{bytes: Uint8Array, offsets: Float64Array}>
@@ -596,6 +598,104 @@ napi_value BpeEncodeWords(napi_env env, napi_callback_info info) {
     return make_u32_array(env, out.data(), (size_t)n);
 }
 
+// document offsets as a Float64Array of non-negative integers (exact below 2^53), D + 1 >= 1 entries
+bool get_doc_offsets(napi_env env, napi_value v, std::vector<uint64_t>* out) {
+    bool is_ta = false;
+    napi_typedarray_type type = napi_uint8_array;
+    size_t n = 0, off = 0;
+    void* raw = nullptr;
+    napi_value ab;
+    if (napi_is_typedarray(env, v, &is_ta) != napi_ok || !is_ta ||
+        napi_get_typedarray_info(env, v, &type, &n, &raw, &ab, &off) != napi_ok || type != napi_float64_array || n < 1)
+        return false;
+    const double* d = static_cast<const double*>(raw);
+    out->resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        if (!(d[i] >= 0 && d[i] <= 9007199254740992.0) || d[i] != (double)(uint64_t)d[i]) return false;
+        (*out)[i] = (uint64_t)d[i];
+    }
+    return true;
+}
+
+napi_value make_f64_array(napi_env env, const std::vector<uint64_t>& v) {
+    napi_value ab, ta;
+    void* dst = nullptr;
+    NAPI_CALL(env, napi_create_arraybuffer(env, v.size() * 8, &dst, &ab));
+    for (size_t i = 0; i < v.size(); ++i) static_cast<double*>(dst)[i] = (double)v[i];
+    NAPI_CALL(env, napi_create_typedarray(env, napi_float64_array, v.size(), ab, 0, &ta));
+    return ta;
+}
+
+// bpeEncodeWordsBatch(ctx, bpe, bytes, offsets, wordStarts | null, mode) -> { tokens, offsets }: many
+// documents in one call (gbpe_bpe_encode_words_batch), each encoded as bpeEncodeWords encodes it alone
+napi_value BpeEncodeWordsBatch(napi_env env, napi_callback_info info) {
+    size_t argc = 6;
+    napi_value argv[6];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Ctx* c = argc >= 1 ? unwrap_external<Ctx>(env, argv[0]) : nullptr;
+    Bpe* b = argc >= 2 ? unwrap_external<Bpe>(env, argv[1]) : nullptr;
+    const uint8_t *data = nullptr, *ws = nullptr;
+    size_t len = 0, ws_len = 0;
+    uint32_t mode = 0;
+    std::vector<uint64_t> doc_off;
+    bool ok = ctx_usable(c) && b && b->bpe && argc >= 6 && get_bytes(env, argv[2], &data, &len) &&
+              get_doc_offsets(env, argv[3], &doc_off) && napi_get_value_uint32(env, argv[5], &mode) == napi_ok;
+    bool has_ws = false;
+    if (ok) {
+        napi_valuetype vt;
+        ok = napi_typeof(env, argv[4], &vt) == napi_ok;
+        has_ws = ok && vt != napi_null && vt != napi_undefined;
+        if (has_ws) ok = get_bytes(env, argv[4], &ws, &ws_len) && ws_len == len;
+    }
+    if (!ok) {
+        napi_throw_type_error(env, nullptr,
+                              "bpeEncodeWordsBatch(ctx, bpe, Uint8Array, offsets: Float64Array of non-negative integers, "
+                              "wordStarts: Uint8Array of the same length | null, mode)");
+        return nullptr;
+    }
+    static const uint8_t kNoByte = 0;
+    if (has_ws && !ws) ws = &kNoByte;   // (an empty mask still goes with mode 1)
+    std::vector<uint32_t> out(len ? len : 1);
+    std::vector<uint64_t> tok_off(doc_off.size(), 0);
+    uint64_t n = 0;
+    std::unique_lock<std::mutex> g(c->mu);
+    int rc = gbpe_bpe_encode_words_batch(c->ctx, b->bpe, data, len, doc_off.data(), doc_off.size() - 1,
+                                         has_ws ? ws : nullptr, mode, out.data(), out.size(), tok_off.data(), &n);
+    g.unlock();
+    if (rc != GBPE_OK) return throw_status(env, c->ctx, "bpe encode batch", rc);
+    napi_value obj;
+    NAPI_CALL(env, napi_create_object(env, &obj));
+    NAPI_CALL(env, napi_set_named_property(env, obj, "tokens", make_u32_array(env, out.data(), (size_t)n)));
+    NAPI_CALL(env, napi_set_named_property(env, obj, "offsets", make_f64_array(env, tok_off)));
+    return obj;
+}
+
+// pretokenizeGpt4Batch(ctx, bytes, offsets) -> Uint8Array: each document's own GPT-4 word starts
+// (gbpe_pretokenize_gpt4_batch)
+napi_value PretokenizeGpt4Batch(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Ctx* c = argc >= 1 ? unwrap_external<Ctx>(env, argv[0]) : nullptr;
+    const uint8_t* data = nullptr;
+    size_t len = 0;
+    std::vector<uint64_t> doc_off;
+    if (!ctx_usable(c) || argc < 3 || !get_bytes(env, argv[1], &data, &len) || !get_doc_offsets(env, argv[2], &doc_off)) {
+        napi_throw_type_error(env, nullptr,
+                              "pretokenizeGpt4Batch(ctx, Uint8Array, offsets: Float64Array of non-negative integers)");
+        return nullptr;
+    }
+    napi_value ab, ta;
+    void* dst = nullptr;
+    NAPI_CALL(env, napi_create_arraybuffer(env, len, &dst, &ab));
+    std::unique_lock<std::mutex> g(c->mu);
+    int rc = gbpe_pretokenize_gpt4_batch(c->ctx, data, len, doc_off.data(), doc_off.size() - 1, static_cast<uint8_t*>(dst));
+    g.unlock();
+    if (rc != GBPE_OK) return throw_status(env, c->ctx, "pretokenizeGpt4Batch", rc);
+    NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, len, ab, 0, &ta));
+    return ta;
+}
+
 struct EncodeWork {
     napi_async_work work = nullptr;
     napi_deferred deferred = nullptr;
@@ -990,6 +1090,8 @@ napi_value Init(napi_env env, napi_value exports) {
         {"trieFree", nullptr, TrieFree, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"encode", nullptr, Encode, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"encodeBatch", nullptr, EncodeBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"bpeEncodeWordsBatch", nullptr, BpeEncodeWordsBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"pretokenizeGpt4Batch", nullptr, PretokenizeGpt4Batch, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"vocabUpload", nullptr, VocabUpload, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"vocabFree", nullptr, VocabFree, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"decode", nullptr, Decode, nullptr, nullptr, nullptr, napi_default, nullptr},

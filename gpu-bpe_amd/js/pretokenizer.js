@@ -8,6 +8,7 @@
  * NFC-normalises first, which leaves NFC text unchanged).  Node 12 syntax.
  */
 import { native } from './native.js';
+import { flattenDocuments } from './merge-encoder.js';
 
 export class GpuPreTokenizer {
     constructor(engine) {
@@ -20,6 +21,17 @@ export class GpuPreTokenizer {
         const bytes = rawBytes instanceof Uint8Array ? rawBytes : new Uint8Array(rawBytes);
         const wordStarts = native().pretokenizeGpt4(this._engine.device, bytes);
         return { bytes, wordStarts };
+    }
+
+    /**
+     * Word starts of many documents in one call: docs is an array of Uint8Array, or one
+     * Uint8Array with its D + 1 offsets.  Returns { bytes, wordStarts, offsets } over the
+     * concatenation; each document's part is exactly preTokenizeBytes of it alone.
+     */
+    preTokenizeBatch(docs, offsets) {
+        const flat = flattenDocuments(docs, offsets);
+        const wordStarts = native().pretokenizeGpt4Batch(this._engine.device, flat.bytes, flat.offsets);
+        return { bytes: flat.bytes, wordStarts: wordStarts, offsets: flat.offsets };
     }
 
     preTokenize(text) {

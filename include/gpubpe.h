@@ -29,7 +29,9 @@
 extern "C" {
 #endif
 
-#define GBPE_ABI_VERSION 9   /* 9: word-bounded merge-rank encode (gbpe_bpe_encode_words*, gbpe_bpe_encode_last_timing);
+#define GBPE_ABI_VERSION 10  /* 10: many documents in one call for the word starts and the word-bounded encode
+                                 (gbpe_pretokenize_gpt4_batch*, gbpe_bpe_encode_words_batch*);
+                                 9: word-bounded merge-rank encode (gbpe_bpe_encode_words*, gbpe_bpe_encode_last_timing);
                                  8: device decode (gbpe_vocab_upload, gbpe_decode*, gbpe_decode_batch*);
                                  7: gbpe_encode_batch, gbpe_encode_batch_device (many documents in one call);
                                  6: pair_candidates, pair_rejected added at the end of the stats; 5: paired_merges
@@ -97,6 +99,22 @@ int gbpe_word_boundary(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, uint8_t*
  * d_bytes[0, n) and writes only d_ws[0, n), on the context's stream. */
 int gbpe_pretokenize_gpt4(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, uint8_t* ws_out);
 int gbpe_pretokenize_gpt4_device(gbpe_ctx* ctx, const void* d_bytes, uint64_t n, void* d_ws);
+/* The same mask for many documents laid end to end (gbpe_encode_batch's
+ * layout: doc_off has n_docs + 1 non-decreasing entries from 0 to n, empty documents
+ * allowed): ws_out[doc_off[d] .. doc_off[d+1]) is exactly what gbpe_pretokenize_gpt4
+ * gives for document d alone — the digit runs, the contraction look-arounds and a
+ * sequence cut at a document's end never see the neighbouring document.  Each
+ * document has that function's domain.  This is the word_starts gbpe_train takes for
+ * a corpus of documents.  n == 0 or n_docs == 0: GBPE_OK, nothing launched.  Bad
+ * offsets: GBPE_E_INVALID; the host form checks them before anything is launched.
+ * The _device form takes d_bytes and d_ws of any alignment and d_doc_off (u64)
+ * 8-byte aligned; its first kernel checks the offsets and bad ones return before
+ * any other kernel runs, with d_ws untouched.  It returns after the kernels have
+ * finished (the single-buffer _device form does not wait). */
+int gbpe_pretokenize_gpt4_batch(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, const uint64_t* doc_off,
+                                uint64_t n_docs, uint8_t* ws_out);
+int gbpe_pretokenize_gpt4_batch_device(gbpe_ctx* ctx, const void* d_bytes, uint64_t n, const void* d_doc_off,
+                                       uint64_t n_docs, void* d_ws);
 
 /* ── training (replaces trainer.js:149-335 BPETrainer.train over the
  *    train.wgsl kernels, training-pipeline.js:178-222 encodeBatch) ─────── */
@@ -390,8 +408,39 @@ int gbpe_bpe_encode_words(gbpe_ctx* ctx, gbpe_bpe* bpe, const uint8_t* bytes, ui
 int gbpe_bpe_encode_words_device(gbpe_ctx* ctx, gbpe_bpe* bpe, const void* d_bytes, uint64_t n,
                                  const void* d_word_starts, uint32_t words_mode, void* d_out, uint64_t out_cap,
                                  uint64_t* n_out);
-/* device ms of the last word encode's kernels: the word-start kernels, k_me_long
- * plus the walk, the count scan plus the compaction */
+/* Many documents in one call (gbpe_encode_batch's layout of bytes,
+ * doc_off, out and tok_off): out[tok_off[d] .. tok_off[d+1]) is exactly what
+ * gbpe_bpe_encode_words returns for document d alone in the same mode, and no token
+ * crosses a document start.  GBPE_WORDS_NONE: each document gets gbpe_bpe_encode's
+ * tokens.  GBPE_WORDS_MASK: word_starts has n entries, one mask over the
+ * concatenation; a document's first byte starts a word whatever it says.
+ * GBPE_WORDS_HEURISTIC, GBPE_WORDS_GPT4: each document's own mask
+ * (gbpe_pretokenize_gpt4_batch's for GPT4).  The mode and mask rules are
+ * gbpe_bpe_encode_words's.  On GBPE_E_CAPACITY *n_out holds the required token
+ * count, tok_off is complete, the first out_cap tokens are in place and nothing is
+ * written at or beyond out[out_cap]; out == NULL with out_cap == 0 asks for the
+ * size.  n == 0 or n_docs == 0: GBPE_OK, *n_out = 0, every tok_off entry 0.  Bad
+ * offsets: GBPE_E_INVALID with nothing written; the host form checks them before
+ * anything is launched.  The input limit is gbpe_bpe_encode_words's, one device
+ * allocation for the whole batch: larger inputs are not split into groups of whole
+ * documents the way gbpe_encode_batch splits them. */
+int gbpe_bpe_encode_words_batch(gbpe_ctx* ctx, gbpe_bpe* bpe, const uint8_t* bytes, uint64_t n, const uint64_t* doc_off,
+                                uint64_t n_docs, const uint8_t* word_starts, uint32_t words_mode, uint32_t* out,
+                                uint64_t out_cap, uint64_t* tok_off, uint64_t* n_out);
+/* Device-resident variant, on the context's stream: d_bytes and d_word_starts of any
+ * alignment, d_doc_off and d_tok_off (u64) 8-byte aligned, d_out (u32) 4-byte
+ * aligned, else GBPE_E_INVALID.  Only [0, n) of the inputs and d_doc_off[0, n_docs]
+ * are read; only d_out[0, min(total, out_cap)) and d_tok_off[0, n_docs] are written.
+ * The first kernel checks the offsets; its verdict comes back with the call's first
+ * read-back, before anything is written to d_out or d_tok_off.  Work buffers come
+ * from the context's pool; the call synchronises twice, as the single-buffer one. */
+int gbpe_bpe_encode_words_batch_device(gbpe_ctx* ctx, gbpe_bpe* bpe, const void* d_bytes, uint64_t n,
+                                       const void* d_doc_off, uint64_t n_docs, const void* d_word_starts,
+                                       uint32_t words_mode, void* d_out, uint64_t out_cap, void* d_tok_off,
+                                       uint64_t* n_out);
+/* device ms of the last word encode's kernels: the word-start kernels (a batch call:
+ * with the document flags), k_me_long plus the walk, the count scan plus the
+ * compaction (a batch call: with the document token offsets) */
 int gbpe_bpe_encode_last_timing(gbpe_ctx* ctx, double* ms_starts, double* ms_walk, double* ms_compact);
 
 /* device ms of the last encode's kernels (walk, scan, compact); after a batch call:
