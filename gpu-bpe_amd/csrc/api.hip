@@ -141,9 +141,12 @@ void gbpe_pool_trim(gbpe_ctx* ctx) {
     pool_release(ctx->hpool, true, 0);
 }
 
-// device memory outside the pool (encode, pre-tokenizer and merge-encode buffers):
-// a failed hipMalloc gives the pool's idle blocks back and tries once more, so a
-// context that trained first can still encode
+// device memory outside the pool: the context's grown work buffers (GbpeGrowBuf:
+// trie encode, decode, the pre-tokenizer's block aggregates) and what lives as long
+// as its handle (tries, vocabularies, merge tables, the Unicode tables).  A failed
+// hipMalloc gives the pool's idle blocks back and tries once more, so a context
+// that trained first can still encode.  The per-call blocks of the
+// merge-rank encoder and the pre-tokenizer come from the pool (GbpeArray).
 hipError_t gbpe_dev_malloc(gbpe_ctx* ctx, void** p, uint64_t bytes) {
     hipError_t e = hipMalloc(p, bytes ? bytes : 1);
     if (e == hipErrorOutOfMemory) {
@@ -151,6 +154,18 @@ hipError_t gbpe_dev_malloc(gbpe_ctx* ctx, void** p, uint64_t bytes) {
         gbpe_pool_trim(ctx);
         e = hipMalloc(p, bytes ? bytes : 1);
     }
+    return e;
+}
+
+hipError_t GbpeGrowBuf::reserve(gbpe_ctx* ctx, uint64_t need) {
+    if (bytes >= need) return hipSuccess;
+    if (p) {
+        hipStreamSynchronize(ctx->stream);   // (the buffer may still be in use on the stream)
+        free();
+    }
+    const hipError_t e = gbpe_dev_malloc(ctx, &p, need + need / 2);
+    if (e == hipSuccess) bytes = need + need / 2;
+    else p = nullptr;
     return e;
 }
 
@@ -216,15 +231,9 @@ void gbpe_ctx_destroy(gbpe_ctx* ctx) {
     if (!ctx) return;
     hipSetDevice(ctx->device);
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
-    hipFree(ctx->enc_scratch);
-    hipFree(ctx->enc_counts);
-    hipFree(ctx->enc_in);
-    hipFree(ctx->enc_out);
-    hipFree(ctx->enc_docs);
-    hipFree(ctx->dec_in);
-    hipFree(ctx->dec_out);
-    hipFree(ctx->dec_work);
-    hipFree(ctx->pt_agg);
+    for (GbpeGrowBuf* b : {&ctx->enc_scratch, &ctx->enc_counts, &ctx->enc_in, &ctx->enc_out, &ctx->enc_docs, &ctx->dec_in,
+                           &ctx->dec_out, &ctx->dec_work, &ctx->pt_agg})
+        b->free();
     if (ctx->enc_host_total) hipHostFree(ctx->enc_host_total);
     if (pool_debug())
         fprintf(stderr, "[pool] busy at context destroy: device %zu pinned %zu\n", ctx->dpool.busy.size(),

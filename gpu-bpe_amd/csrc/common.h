@@ -32,6 +32,22 @@ struct GbpePool {
     uint64_t idle_bytes = 0, hits = 0, misses = 0;
 };
 
+// One work buffer of a context's encode, decode and pre-tokenise calls, outside the
+// pool (plain hipMalloc through gbpe_dev_malloc): it grows and never shrinks
+// (tokenizer.js:30-46 buffer pool), and its contents do not survive a growth.
+struct GbpeGrowBuf {
+    void* p = nullptr;
+    uint64_t bytes = 0;
+    // room for `need` bytes.  Enough already: nothing happens; otherwise the context's
+    // stream is synchronised, the old buffer freed and need * 1.5 allocated
+    // (amortised growth, tokenizer.js:125-128)
+    hipError_t reserve(gbpe_ctx* ctx, uint64_t need);   // (api.hip)
+    void free() {
+        hipFree(p);
+        p = nullptr, bytes = 0;
+    }
+};
+
 struct gbpe_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -40,19 +56,15 @@ struct gbpe_ctx {
     uint64_t total_mem = 0;
     int num_cu = 0;
     std::string err;
-    // encode pool (tokenizer.js:30-46 buffer pool: grows, never shrinks)
-    void* enc_scratch = nullptr;  uint64_t enc_scratch_bytes = 0;
-    void* enc_counts = nullptr;   uint64_t enc_counts_bytes = 0;
-    void* enc_in = nullptr;       uint64_t enc_in_bytes = 0;
-    void* enc_out = nullptr;      uint64_t enc_out_bytes = 0;
-    void* enc_docs = nullptr;     uint64_t enc_docs_bytes = 0;   // gbpe_encode_batch: per-document table
-    uint32_t* enc_host_total = nullptr;   // pinned, 64 bytes
-    // decode pool, grown the same way: token slice / byte slice of the host forms, prefixes + document offsets
-    void* dec_in = nullptr;       uint64_t dec_in_bytes = 0;
-    void* dec_out = nullptr;      uint64_t dec_out_bytes = 0;
-    void* dec_work = nullptr;     uint64_t dec_work_bytes = 0;
+    // trie encode: chunk tokens; counts + scan state (+ chunk descriptors of a batch); byte / token
+    // slice of the host forms; gbpe_encode_batch's per-document table (+ the host form's offsets)
+    GbpeGrowBuf enc_scratch, enc_counts, enc_in, enc_out, enc_docs;
+    uint32_t* enc_host_total = nullptr;   // pinned, 64 bytes: every call's read-back cell
+    // decode: token slice / byte slice of the host forms, prefixes + document offsets
+    GbpeGrowBuf dec_in, dec_out, dec_work;
     double dec_ms[3] = {0, 0, 0};
-    void* pt_agg = nullptr;       uint64_t pt_agg_bytes = 0;   // pre-tokenizer block aggregates
+    GbpeGrowBuf pt_agg;   // pre-tokenizer block aggregates
+    // (all nine are freed by gbpe_ctx_destroy)
     hipEvent_t ev[8] = {};
     double enc_ms[3] = {0, 0, 0};
     double bpe_ms[3] = {0, 0, 0};   // word-bounded merge-rank encode: word starts, long + walk, scan + compact

@@ -202,20 +202,6 @@ __global__ __launch_bounds__(256) void k_dec_scatter_plain(const uint32_t* __res
     for (uint32_t j = 0; j < e.y && p + j < lim; ++j) out[p + j] = blob[e.x + j];
 }
 
-int dec_grow(gbpe_ctx* ctx, void** p, uint64_t* have, uint64_t need) {
-    if (*have >= need) return GBPE_OK;
-    if (*p) {
-        hipStreamSynchronize(ctx->stream);
-        hipFree(*p);
-        *p = nullptr;
-        *have = 0;
-    }
-    const uint64_t sz = need + need / 2;   // 1.5x amortised growth, as the encode buffers
-    GBPE_HIP(ctx, dev_malloc(ctx, p, sz));
-    *have = sz;
-    return GBPE_OK;
-}
-
 int dec_offsets_error(gbpe_ctx* ctx, uint32_t bad) {
     return gbpe_set_error(ctx, GBPE_E_INVALID, "decode batch: token offsets %s",
                           (bad & DEC_BAD_FIRST)   ? "do not start at 0"
@@ -244,11 +230,10 @@ struct DecPlan {   // device arrays of one pass over n tokens, inside ctx->dec_w
 int dec_plan(gbpe_ctx* ctx, uint64_t n, DecPlan* pl) {
     pl->nblk = gbpe_div_up(n, SCAN_BLK);
     const uint64_t head = ((pl->nblk + 2) * 8 + 15) & ~15ull;
-    const int rc = dec_grow(ctx, &ctx->dec_work, &ctx->dec_work_bytes, head + n * 4 + 16);
-    if (rc != GBPE_OK) return rc;
-    pl->blocksum = (uint64_t*)ctx->dec_work;
+    GBPE_HIP(ctx, ctx->dec_work.reserve(ctx, head + n * 4 + 16));
+    pl->blocksum = (uint64_t*)ctx->dec_work.p;
     pl->flag = (uint32_t*)(pl->blocksum + pl->nblk + 1);
-    pl->local = (uint32_t*)((uint8_t*)ctx->dec_work + head);
+    pl->local = (uint32_t*)((uint8_t*)ctx->dec_work.p + head);
     return GBPE_OK;
 }
 
@@ -346,10 +331,10 @@ int decode_host_impl(gbpe_ctx* ctx, gbpe_vocab* v, const uint32_t* tokens, uint6
         const uint64_t tok_bytes = (len * 4 + 15) & ~15ull;
         DecPlan pl;
         int rc = dec_plan(ctx, len, &pl);
-        if (rc == GBPE_OK) rc = dec_grow(ctx, &ctx->dec_in, &ctx->dec_in_bytes, tok_bytes + 2 * m * 8 + 16);
         if (rc != GBPE_OK) return rc;
-        uint32_t* d_tok = (uint32_t*)ctx->dec_in;
-        uint64_t* d_rel = (uint64_t*)((uint8_t*)ctx->dec_in + tok_bytes);
+        GBPE_HIP(ctx, ctx->dec_in.reserve(ctx, tok_bytes + 2 * m * 8 + 16));
+        uint32_t* d_tok = (uint32_t*)ctx->dec_in.p;
+        uint64_t* d_rel = (uint64_t*)((uint8_t*)ctx->dec_in.p + tok_bytes);
         uint64_t* d_boff = d_rel + m;
         GBPE_HIP(ctx, hipMemcpyAsync(d_tok, tokens + s0, len * 4, hipMemcpyHostToDevice, ctx->stream));
         if (m) {
@@ -363,10 +348,10 @@ int decode_host_impl(gbpe_ctx* ctx, gbpe_vocab* v, const uint32_t* tokens, uint6
         if (m) GBPE_HIP(ctx, hipMemcpyAsync(byte_off + e0, d_boff, m * 8, hipMemcpyDeviceToHost, ctx->stream));
         const uint64_t fit = total < out_cap ? std::min(t, out_cap - total) : 0;   // never at or beyond out[out_cap]
         if (fit) {
-            rc = dec_grow(ctx, &ctx->dec_out, &ctx->dec_out_bytes, fit + 16);
-            if (rc == GBPE_OK) rc = decode_scatter(ctx, v, d_tok, len, pl, (uint8_t*)ctx->dec_out, fit);
+            GBPE_HIP(ctx, ctx->dec_out.reserve(ctx, fit + 16));
+            rc = decode_scatter(ctx, v, d_tok, len, pl, (uint8_t*)ctx->dec_out.p, fit);
             if (rc != GBPE_OK) return rc;
-            GBPE_HIP(ctx, hipMemcpyAsync(out + total, ctx->dec_out, fit, hipMemcpyDeviceToHost, ctx->stream));
+            GBPE_HIP(ctx, hipMemcpyAsync(out + total, ctx->dec_out.p, fit, hipMemcpyDeviceToHost, ctx->stream));
         }
         GBPE_HIP(ctx, hipStreamSynchronize(ctx->stream));
         for (uint64_t e = e0; e < e1; ++e) byte_off[e] += total;

@@ -352,7 +352,6 @@ __global__ __launch_bounds__(256) void k_chunk_compact4(const T* __restrict__ sc
 // the vector stores aligned); the exclusive scans of both give chunk_base /
 // scr_base.  The scratch is then O(n + n_docs) elements, not nchunks * cs.
 constexpr int DOC_TPB = 1024;   // documents per table block (one lane each)
-constexpr uint32_t DOC_BAD_ORDER = 1u, DOC_BAD_FIRST = 2u, DOC_BAD_LAST = 4u;
 
 struct DocTotals {   // read back once per call (the grid and the scratch are sized from it)
     uint64_t nchunks, scr_elems, invalid;
@@ -391,9 +390,9 @@ __global__ __launch_bounds__(DOC_TPB) void k_doc_table(const uint64_t* __restric
     if (d < n_docs) {
         const uint64_t a = doc_off[d], b = doc_off[d + 1];
         uint32_t bad = 0;
-        if (b < a || b > n) bad |= DOC_BAD_ORDER;   // (b > n: a later entry decreases or the last is not n)
-        if (d == 0 && a != 0) bad |= DOC_BAD_FIRST;
-        if (d == n_docs - 1 && b != n) bad |= DOC_BAD_LAST;
+        if (b < a || b > n) bad |= GBPE_DOC_BAD_ORDER;   // (b > n: a later entry decreases or the last is not n)
+        if (d == 0 && a != 0) bad |= GBPE_DOC_BAD_FIRST;
+        if (d == n_docs - 1 && b != n) bad |= GBPE_DOC_BAD_LAST;
         if (bad) {
             atomicOr(invalid, bad);
         } else {
@@ -883,20 +882,6 @@ extern "C" void gbpe_trie_free(gbpe_trie* tr) {
 
 namespace {
 
-int grow(gbpe_ctx* ctx, void** p, uint64_t* have, uint64_t need) {
-    if (*have >= need) return GBPE_OK;
-    if (*p) {
-        hipStreamSynchronize(ctx->stream);
-        hipFree(*p);
-        *p = nullptr;
-        *have = 0;
-    }
-    const uint64_t sz = need + need / 2;   // 1.5x amortised growth (tokenizer.js:125-128)
-    GBPE_HIP(ctx, dev_malloc(ctx, p, sz));
-    *have = sz;
-    return GBPE_OK;
-}
-
 uint32_t effective_cs(const gbpe_trie* tr, uint32_t cs) {
     if (cs) return cs;
     // tokenizer.js:67-68 adaptive chunk
@@ -912,11 +897,9 @@ int encode_device_impl(gbpe_ctx* ctx, gbpe_trie* tr, const uint8_t* d_in, uint64
     const bool narrow = tr->max_token_id < 65536u;   // raw-byte fallbacks are < 256
     const uint64_t esz = narrow ? 2 : 4;
     const uint64_t nblk = gbpe_div_up(nchunks, SCAN_BLK);
-    int rc = grow(ctx, &ctx->enc_scratch, &ctx->enc_scratch_bytes, nchunks * cs * esz + 16);
-    if (rc == GBPE_OK)
-        rc = grow(ctx, &ctx->enc_counts, &ctx->enc_counts_bytes, nchunks * 8 + nblk * 8 + 64);
-    if (rc != GBPE_OK) return rc;
-    uint32_t* counts = (uint32_t*)ctx->enc_counts;
+    GBPE_HIP(ctx, ctx->enc_scratch.reserve(ctx, nchunks * cs * esz + 16));
+    GBPE_HIP(ctx, ctx->enc_counts.reserve(ctx, nchunks * 8 + nblk * 8 + 64));
+    uint32_t* counts = (uint32_t*)ctx->enc_counts.p;
     uint32_t* local = counts + nchunks;
     uint64_t* blocksum = (uint64_t*)(((uintptr_t)(local + nchunks) + 15) & ~(uintptr_t)15);
     uint64_t* d_total = blocksum + nblk + 1;
@@ -929,16 +912,16 @@ int encode_device_impl(gbpe_ctx* ctx, gbpe_trie* tr, const uint8_t* d_in, uint64
     const uint32_t nrec2 = tr->nrec + 256;
     if (packed && narrow)
         hipLaunchKernelGGL(k_trie_walk_v5<uint16_t>, dim3(gw), dim3(WALK_TPB), 0, s, d_in, n, cs, tr->rec2, nrec2,
-                           tr->root_base, (uint16_t*)ctx->enc_scratch, counts, nchunks);
+                           tr->root_base, (uint16_t*)ctx->enc_scratch.p, counts, nchunks);
     else if (packed)
         hipLaunchKernelGGL(k_trie_walk_v5<uint32_t>, dim3(gw), dim3(WALK_TPB), 0, s, d_in, n, cs, tr->rec2, nrec2,
-                           tr->root_base, (uint32_t*)ctx->enc_scratch, counts, nchunks);
+                           tr->root_base, (uint32_t*)ctx->enc_scratch.p, counts, nchunks);
     else if (narrow)
         hipLaunchKernelGGL(k_trie_walk<uint16_t>, dim3(gw), dim3(WALK_TPB), 0, s, d_in, n, cs, tr->rec, tr->nrec,
-                           tr->root, (uint16_t*)ctx->enc_scratch, counts, nchunks);
+                           tr->root, (uint16_t*)ctx->enc_scratch.p, counts, nchunks);
     else
         hipLaunchKernelGGL(k_trie_walk<uint32_t>, dim3(gw), dim3(WALK_TPB), 0, s, d_in, n, cs, tr->rec, tr->nrec,
-                           tr->root, (uint32_t*)ctx->enc_scratch, counts, nchunks);
+                           tr->root, (uint32_t*)ctx->enc_scratch.p, counts, nchunks);
     GBPE_LAUNCH_CHECK(ctx);
     GBPE_HIP(ctx, hipEventRecord(ctx->ev[1], s));
     hipLaunchKernelGGL(k_chunk_scan1, dim3((uint32_t)nblk), dim3(SCAN_TPB), 0, s, (const uint32_t*)counts, nchunks, local,
@@ -948,11 +931,11 @@ int encode_device_impl(gbpe_ctx* ctx, gbpe_trie* tr, const uint8_t* d_in, uint64
     GBPE_HIP(ctx, hipEventRecord(ctx->ev[2], s));
     const uint32_t gc4 = (uint32_t)gbpe_div_up(nchunks, 4 * CPW);
     if (narrow)
-        hipLaunchKernelGGL(k_chunk_compact4<uint16_t>, dim3(gc4), dim3(256), 0, s, (const uint16_t*)ctx->enc_scratch,
+        hipLaunchKernelGGL(k_chunk_compact4<uint16_t>, dim3(gc4), dim3(256), 0, s, (const uint16_t*)ctx->enc_scratch.p,
                            (const uint32_t*)counts, (const uint32_t*)local, (const uint64_t*)blocksum, nchunks, cs, d_out,
                            out_cap);
     else
-        hipLaunchKernelGGL(k_chunk_compact4<uint32_t>, dim3(gc4), dim3(256), 0, s, (const uint32_t*)ctx->enc_scratch,
+        hipLaunchKernelGGL(k_chunk_compact4<uint32_t>, dim3(gc4), dim3(256), 0, s, (const uint32_t*)ctx->enc_scratch.p,
                            (const uint32_t*)counts, (const uint32_t*)local, (const uint64_t*)blocksum, nchunks, cs, d_out,
                            out_cap);
     GBPE_LAUNCH_CHECK(ctx);
@@ -981,13 +964,6 @@ uint64_t doc_table_bytes(uint64_t n_docs) {
     return 2 * (n_docs + 1) * 8 + 2 * (ndblk + 1) * 8 + sizeof(DocTotals) + 8 + 64;
 }
 
-int doc_offsets_error(gbpe_ctx* ctx, uint32_t bad) {
-    return gbpe_set_error(ctx, GBPE_E_INVALID, "encode batch: document offsets %s",
-                          (bad & DOC_BAD_FIRST)   ? "do not start at 0"
-                          : (bad & DOC_BAD_ORDER) ? "decrease (or pass the end of the bytes)"
-                                                  : "do not end at the byte count");
-}
-
 // The batch pipeline on device buffers (n, n_docs > 0): table + scans (one
 // readback: the chunk count sizes the grid, the slot total the scratch),
 // descriptors, walk, count scan, compact, document token offsets.
@@ -998,9 +974,8 @@ int encode_batch_device_impl(gbpe_ctx* ctx, gbpe_trie* tr, const uint8_t* d_in, 
     const bool narrow = tr->max_token_id < 65536u;   // raw-byte fallbacks are < 256
     const uint64_t esz = narrow ? 2 : 4;
     const uint64_t ndblk = gbpe_div_up(n_docs, DOC_TPB);
-    int rc = grow(ctx, &ctx->enc_docs, &ctx->enc_docs_bytes, doc_table_bytes(n_docs));
-    if (rc != GBPE_OK) return rc;
-    uint64_t* chunk_base = (uint64_t*)ctx->enc_docs;
+    GBPE_HIP(ctx, ctx->enc_docs.reserve(ctx, doc_table_bytes(n_docs)));
+    uint64_t* chunk_base = (uint64_t*)ctx->enc_docs.p;
     uint64_t* scr_base = chunk_base + n_docs + 1;
     uint64_t* blk_ch = scr_base + n_docs + 1;
     uint64_t* blk_scr = blk_ch + ndblk + 1;
@@ -1020,17 +995,14 @@ int encode_batch_device_impl(gbpe_ctx* ctx, gbpe_trie* tr, const uint8_t* d_in, 
     GBPE_HIP(ctx, hipStreamSynchronize(s));
     DocTotals tot;
     memcpy(&tot, ctx->enc_host_total, sizeof(tot));
-    if (tot.invalid) return doc_offsets_error(ctx, (uint32_t)tot.invalid);   // nothing else was launched
+    if (tot.invalid) return gbpe_doc_offsets_error(ctx, "encode batch", (uint32_t)tot.invalid);   // nothing else was launched
     const uint64_t nchunks = tot.nchunks;
     if (nchunks == 0) return gbpe_set_error(ctx, GBPE_E_INTERNAL, "encode batch: no chunks for %llu bytes", (unsigned long long)n);
     const uint64_t nblk = gbpe_div_up(nchunks, SCAN_BLK);
     // scratch: one rounded slot per document, O(n + n_docs) elements
-    rc = grow(ctx, &ctx->enc_scratch, &ctx->enc_scratch_bytes, tot.scr_elems * esz + 16);
-    if (rc == GBPE_OK)
-        rc = grow(ctx, &ctx->enc_counts, &ctx->enc_counts_bytes,
-                  nchunks * 8 + nblk * 8 + 64 + 16 + nchunks * sizeof(ChunkDesc));
-    if (rc != GBPE_OK) return rc;
-    uint32_t* counts = (uint32_t*)ctx->enc_counts;
+    GBPE_HIP(ctx, ctx->enc_scratch.reserve(ctx, tot.scr_elems * esz + 16));
+    GBPE_HIP(ctx, ctx->enc_counts.reserve(ctx, nchunks * 8 + nblk * 8 + 64 + 16 + nchunks * sizeof(ChunkDesc)));
+    uint32_t* counts = (uint32_t*)ctx->enc_counts.p;
     uint32_t* local = counts + nchunks;
     uint64_t* blocksum = (uint64_t*)(((uintptr_t)(local + nchunks) + 15) & ~(uintptr_t)15);
     uint64_t* d_total = blocksum + nblk + 1;
@@ -1046,16 +1018,16 @@ int encode_batch_device_impl(gbpe_ctx* ctx, gbpe_trie* tr, const uint8_t* d_in, 
     const uint32_t nrec2 = tr->nrec + 256;
     if (packed && narrow)
         hipLaunchKernelGGL(k_trie_walk_v5_batch<uint16_t>, dim3(gw), dim3(WALK_TPB), 0, s, d_in, n, (const ChunkDesc*)desc,
-                           tr->rec2, nrec2, tr->root_base, (uint16_t*)ctx->enc_scratch, counts, nchunks);
+                           tr->rec2, nrec2, tr->root_base, (uint16_t*)ctx->enc_scratch.p, counts, nchunks);
     else if (packed)
         hipLaunchKernelGGL(k_trie_walk_v5_batch<uint32_t>, dim3(gw), dim3(WALK_TPB), 0, s, d_in, n, (const ChunkDesc*)desc,
-                           tr->rec2, nrec2, tr->root_base, (uint32_t*)ctx->enc_scratch, counts, nchunks);
+                           tr->rec2, nrec2, tr->root_base, (uint32_t*)ctx->enc_scratch.p, counts, nchunks);
     else if (narrow)
         hipLaunchKernelGGL(k_trie_walk_batch<uint16_t>, dim3(gw), dim3(WALK_TPB), 0, s, d_in, n, (const ChunkDesc*)desc,
-                           tr->rec, tr->nrec, tr->root, (uint16_t*)ctx->enc_scratch, counts, nchunks);
+                           tr->rec, tr->nrec, tr->root, (uint16_t*)ctx->enc_scratch.p, counts, nchunks);
     else
         hipLaunchKernelGGL(k_trie_walk_batch<uint32_t>, dim3(gw), dim3(WALK_TPB), 0, s, d_in, n, (const ChunkDesc*)desc,
-                           tr->rec, tr->nrec, tr->root, (uint32_t*)ctx->enc_scratch, counts, nchunks);
+                           tr->rec, tr->nrec, tr->root, (uint32_t*)ctx->enc_scratch.p, counts, nchunks);
     GBPE_LAUNCH_CHECK(ctx);
     GBPE_HIP(ctx, hipEventRecord(ctx->ev[1], s));
     hipLaunchKernelGGL(k_chunk_scan1, dim3((uint32_t)nblk), dim3(SCAN_TPB), 0, s, (const uint32_t*)counts, nchunks, local,
@@ -1066,11 +1038,11 @@ int encode_batch_device_impl(gbpe_ctx* ctx, gbpe_trie* tr, const uint8_t* d_in, 
     const uint32_t gc4 = (uint32_t)gbpe_div_up(nchunks, 4 * CPW);
     if (narrow)
         hipLaunchKernelGGL(k_chunk_compact4_batch<uint16_t>, dim3(gc4), dim3(256), 0, s,
-                           (const uint16_t*)ctx->enc_scratch, (const ChunkDesc*)desc, (const uint32_t*)counts,
+                           (const uint16_t*)ctx->enc_scratch.p, (const ChunkDesc*)desc, (const uint32_t*)counts,
                            (const uint32_t*)local, (const uint64_t*)blocksum, nchunks, d_out, out_cap);
     else
         hipLaunchKernelGGL(k_chunk_compact4_batch<uint32_t>, dim3(gc4), dim3(256), 0, s,
-                           (const uint32_t*)ctx->enc_scratch, (const ChunkDesc*)desc, (const uint32_t*)counts,
+                           (const uint32_t*)ctx->enc_scratch.p, (const ChunkDesc*)desc, (const uint32_t*)counts,
                            (const uint32_t*)local, (const uint64_t*)blocksum, nchunks, d_out, out_cap);
     // (runs whether or not the tokens fit: tok_off is complete on GBPE_E_CAPACITY)
     hipLaunchKernelGGL(k_doc_tok_off, dim3((uint32_t)gbpe_div_up(n_docs + 1, 256)), dim3(256), 0, s,
@@ -1136,10 +1108,8 @@ extern "C" int gbpe_encode_batch(gbpe_ctx* ctx, gbpe_trie* tr, const uint8_t* by
         tok_off[0] = 0;
         return GBPE_OK;
     }
-    if (doc_off[0] != 0) return doc_offsets_error(ctx, DOC_BAD_FIRST);
-    for (uint64_t d = 0; d < n_docs; ++d)
-        if (doc_off[d + 1] < doc_off[d]) return doc_offsets_error(ctx, DOC_BAD_ORDER);
-    if (doc_off[n_docs] != n) return doc_offsets_error(ctx, DOC_BAD_LAST);
+    int rc = gbpe_doc_offsets_check(ctx, "encode batch", doc_off, n_docs, n);
+    if (rc != GBPE_OK) return rc;
     const uint32_t cs = effective_cs(tr, chunk_size);
     if (cs > kBatchMaxChunk) return gbpe_set_error(ctx, GBPE_E_INVALID, "encode batch: chunk size above 2^31");
     if (n == 0) {
@@ -1161,13 +1131,12 @@ extern "C" int gbpe_encode_batch(gbpe_ctx* ctx, gbpe_trie* tr, const uint8_t* by
         g0 = g1;
     }
     const uint64_t table = (doc_table_bytes(max_docs) + 15) & ~15ull;
-    int rc = grow(ctx, &ctx->enc_in, &ctx->enc_in_bytes, max_bytes + 64);
-    if (rc == GBPE_OK) rc = grow(ctx, &ctx->enc_out, &ctx->enc_out_bytes, max_bytes * 4 + 16);   // <= 1 token per byte
-    if (rc == GBPE_OK) rc = grow(ctx, &ctx->enc_docs, &ctx->enc_docs_bytes, table + 2 * (max_docs + 1) * 8);
-    if (rc != GBPE_OK) return rc;
-    uint8_t* d_in = (uint8_t*)ctx->enc_in;
-    uint32_t* d_out = (uint32_t*)ctx->enc_out;
-    uint64_t* d_doc_off = (uint64_t*)((uint8_t*)ctx->enc_docs + table);   // (behind the impl's table)
+    GBPE_HIP(ctx, ctx->enc_in.reserve(ctx, max_bytes + 64));
+    GBPE_HIP(ctx, ctx->enc_out.reserve(ctx, max_bytes * 4 + 16));   // <= 1 token per byte
+    GBPE_HIP(ctx, ctx->enc_docs.reserve(ctx, table + 2 * (max_docs + 1) * 8));
+    uint8_t* d_in = (uint8_t*)ctx->enc_in.p;
+    uint32_t* d_out = (uint32_t*)ctx->enc_out.p;
+    uint64_t* d_doc_off = (uint64_t*)((uint8_t*)ctx->enc_docs.p + table);   // (behind the impl's table)
     uint64_t* d_tok_off = d_doc_off + max_docs + 1;
     std::vector<uint64_t> rel;
     uint64_t total = 0;
@@ -1223,15 +1192,15 @@ extern "C" int gbpe_encode(gbpe_ctx* ctx, gbpe_trie* tr, const uint8_t* bytes, u
     *n_out = 0;
     if (n == 0) return GBPE_OK;   // tokenizer.js:175
     const uint32_t cs = effective_cs(tr, chunk_size);
-    int rc = grow(ctx, &ctx->enc_in, &ctx->enc_in_bytes, gbpe_div_up(n, 4) * 4 + 16);
-    if (rc == GBPE_OK) rc = grow(ctx, &ctx->enc_out, &ctx->enc_out_bytes, n * 4 + 16);   // <= 1 token per byte
-    if (rc != GBPE_OK) return rc;
+    GBPE_HIP(ctx, ctx->enc_in.reserve(ctx, gbpe_div_up(n, 4) * 4 + 16));
+    GBPE_HIP(ctx, ctx->enc_out.reserve(ctx, n * 4 + 16));   // <= 1 token per byte
     const uint64_t unit = (uint64_t)cs * 64;
     // (test override: many slices on small inputs)
     const uint64_t want = (uint64_t)std::max<long>(1, gbpe_debug_knob("encode_slice", (long)kEncSlice));
     const uint64_t slice = std::max<uint64_t>(unit, (want / unit) * unit);
-    uint8_t* d_in = (uint8_t*)ctx->enc_in;
-    uint32_t* d_out = (uint32_t*)ctx->enc_out;
+    uint8_t* d_in = (uint8_t*)ctx->enc_in.p;
+    uint32_t* d_out = (uint32_t*)ctx->enc_out.p;
+    int rc = GBPE_OK;
     if (n <= slice) {
         GBPE_HIP(ctx, hipMemcpyAsync(d_in, bytes, n, hipMemcpyHostToDevice, ctx->stream));
         uint64_t total = 0;

@@ -430,82 +430,7 @@ extern "C" void gbpe_bpe_free(gbpe_bpe* bp) {
     delete bp;
 }
 
-extern "C" int gbpe_bpe_encode(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* bytes, uint64_t n, uint32_t* out,
-                               uint64_t out_cap, uint64_t* n_out) {
-    if (!ctx || !bp || !n_out || (n && !bytes)) return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
-    *n_out = 0;
-    if (n == 0) return GBPE_OK;
-    hipStream_t s = ctx->stream;
-    const uint64_t nchunks = gbpe_div_up(n, ME_CS);
-    const uint64_t nblk = gbpe_div_up(nchunks, SCAN_BLK);
-    // device buffers: input, scratch tokens (<= 1 per byte), counts, bases, scan state, output
-    const uint64_t need = n + 16 + 4 * n + 4 * nchunks + 8 * nchunks + 4 * nchunks + 8 * (nblk + 2) + 4 * n + 64;
-    uint8_t* d = nullptr;
-    GBPE_HIP(ctx, dev_malloc(ctx, &d, need));
-    uint8_t* d_in = d;
-    uint32_t* scratch = (uint32_t*)(((uintptr_t)(d + n + 16) + 15) & ~(uintptr_t)15);
-    uint32_t* counts = scratch + n;
-    uint64_t* base = (uint64_t*)(((uintptr_t)(counts + nchunks) + 15) & ~(uintptr_t)15);
-    uint32_t* local = (uint32_t*)(base + nchunks);
-    uint64_t* blocksum = (uint64_t*)(((uintptr_t)(local + nchunks) + 15) & ~(uintptr_t)15);
-    uint64_t* total = blocksum + nblk + 1;
-    uint32_t* d_out = (uint32_t*)(((uintptr_t)(total + 1) + 15) & ~(uintptr_t)15);
-    hipError_t e = hipMemcpyAsync(d_in, bytes, n, hipMemcpyHostToDevice, s);
-    MeTable t{bp->slots, bp->mask, bp->cross};
-    // long segments: their total length sizes the heap arena (none: no arena)
-    MeArena ar{};
-    uint8_t* da = nullptr;
-    uint64_t* slot = nullptr;
-    unsigned long long* d_long = nullptr;
-    unsigned long long long_total = 0;
-    if (e == hipSuccess) e = dev_malloc(ctx, &slot, nchunks * me_lslot(ME_CS) * sizeof(uint64_t) + 16);
-    if (e == hipSuccess) {
-        d_long = (unsigned long long*)(slot + nchunks * me_lslot(ME_CS));
-        e = hipMemsetAsync(d_long, 0, 8, s);
-    }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL((k_me_long<false, ME_CS>), dim3((uint32_t)gbpe_div_up(nchunks, ME_TPB)), dim3(ME_TPB), 0, s,
-                           (const uint8_t*)d_in, (const uint8_t*)nullptr, n, t, d_long, slot, nchunks);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&long_total, d_long, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && long_total) {
-        e = dev_malloc(ctx, &da, long_total * (3 * sizeof(uint32_t) + 3 * sizeof(uint64_t)) + 64);
-        if (e == hipSuccess) {
-            ar.heap = (uint64_t*)da;
-            ar.tok = (uint32_t*)(ar.heap + 3 * long_total);
-            ar.nxt = ar.tok + long_total;
-            ar.prv = ar.nxt + long_total;
-        }
-    }
-    ar.slot = slot;
-    if (e == hipSuccess)
-        hipLaunchKernelGGL((k_me_walk<false, ME_CS>), dim3((uint32_t)gbpe_div_up(nchunks, ME_TPB)), dim3(ME_TPB), 0, s,
-                           (const uint8_t*)d_in, (const uint8_t*)nullptr, n, t, scratch, counts, base, nchunks, ar);
-    hipLaunchKernelGGL(k_chunk_scan1, dim3((uint32_t)nblk), dim3(SCAN_TPB), 0, s, (const uint32_t*)counts, nchunks,
-                       local, blocksum);
-    hipLaunchKernelGGL(k_chunk_scan2, dim3(1), dim3(SCAN_TPB), 0, s, blocksum, nblk, total);
-    hipLaunchKernelGGL(k_me_compact, dim3((uint32_t)gbpe_div_up(nchunks, 4)), dim3(256), 0, s, (const uint32_t*)scratch,
-                       (const uint32_t*)counts, (const uint64_t*)base, (const uint32_t*)local,
-                       (const uint64_t*)blocksum, nchunks, d_out, n);
-    if (e == hipSuccess) e = hipGetLastError();
-    uint64_t tot = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&tot, total, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && tot <= out_cap && out && tot)
-        e = hipMemcpy(out, d_out, tot * 4, hipMemcpyDeviceToHost);
-    hipFree(d);
-    hipFree(da);
-    hipFree(slot);
-    if (e != hipSuccess) return gbpe_set_error(ctx, GBPE_E_DEVICE, "bpe encode failed: %s", hipGetErrorString(e));
-    *n_out = tot;
-    if (tot > out_cap) return gbpe_set_error(ctx, GBPE_E_CAPACITY, "bpe encode: output needs %llu tokens",
-                                             (unsigned long long)tot);
-    return GBPE_OK;
-}
-
-// ── word-bounded encode, device-resident ──────────────────────
+// ── the pipeline on device buffers: one driver for every entry point ──
 
 namespace {
 
@@ -516,11 +441,19 @@ void me_launch_long(hipStream_t s, const uint8_t* in, const uint8_t* ws, uint64_
                        t, total, slot, nchunks);
 }
 
+// k_me_walk, or with the documents of a batch call (always the word form) k_me_walk_docs
 template <bool WORDS, uint32_t CS>
 void me_launch_walk(hipStream_t s, const uint8_t* in, const uint8_t* ws, uint64_t n, const MeTable& t, uint32_t* scratch,
-                    uint32_t* counts, uint64_t* base, uint64_t nchunks, const MeArena& ar) {
-    hipLaunchKernelGGL((k_me_walk<WORDS, CS>), dim3((uint32_t)gbpe_div_up(nchunks, ME_TPB)), dim3(ME_TPB), 0, s, in, ws, n,
-                       t, scratch, counts, base, nchunks, ar);
+                    uint32_t* counts, uint64_t* base, uint64_t nchunks, const MeArena& ar, const MeDocs* docs) {
+    const dim3 grid((uint32_t)gbpe_div_up(nchunks, ME_TPB));
+    if constexpr (WORDS) {
+        if (docs) {
+            hipLaunchKernelGGL((k_me_walk_docs<CS>), grid, dim3(ME_TPB), 0, s, in, ws, n, t, scratch, counts, base, nchunks,
+                               ar, *docs);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_me_walk<WORDS, CS>), grid, dim3(ME_TPB), 0, s, in, ws, n, t, scratch, counts, base, nchunks, ar);
 }
 
 // the instantiation of a call: no mask at ME_CS, or the word form at cs
@@ -534,92 +467,167 @@ void me_launch_walk(hipStream_t s, const uint8_t* in, const uint8_t* ws, uint64_
 
 inline uint64_t up16(uint64_t x) { return (x + 15) & ~15ull; }
 
-// d_in[0, n) (and, mode MASK, d_ws[0, n)) → d_out[0, min(total, out_cap)); n > 0, the mode checked
-int me_words_device(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* d_in, uint64_t n, const uint8_t* d_ws, uint32_t mode,
-                    uint32_t* d_out, uint64_t out_cap, uint64_t* n_out) {
+struct MeWork {   // the device arrays of one call, each 16-byte aligned inside one pooled block
+    uint32_t* scratch;    // n: a chunk's tokens from its first segment start (<= 1 per byte)
+    uint32_t* counts;     // nchunks
+    uint64_t* base;       // nchunks
+    uint32_t* local;      // nchunks
+    uint64_t* blocksum;   // nblk + 1, then the token total
+    uint64_t* total;
+    uint64_t* slot;       // nchunks * me_lslot(cs): arena offsets of the long segments
+    unsigned long long* back;   // 16 bytes read back after k_me_long: the long-segment total, the offsets' verdict
+    // a batch call (n_docs > 0) only
+    uint32_t* doc_written;   // n_docs
+    uint8_t* mask;           // n
+    uint8_t* flags;          // n, when asked for (GPT-4 rules: the document starts)
+};
+
+hipError_t me_layout(gbpe_ctx* ctx, GbpeArray<uint8_t>& blk, uint64_t n, uint32_t cs, uint64_t nchunks, uint64_t nblk,
+                     uint64_t n_docs, bool flags, MeWork* w) {
+    const uint64_t o_counts = up16(4 * n), o_base = o_counts + up16(4 * nchunks), o_local = o_base + up16(8 * nchunks);
+    const uint64_t o_bsum = o_local + up16(4 * nchunks), o_slot = o_bsum + up16(8 * (nblk + 2));
+    const uint64_t o_back = o_slot + up16(8 * nchunks * me_lslot(cs)), o_docw = o_back + 16;
+    const uint64_t o_mask = o_docw + up16(4 * n_docs), o_flags = o_mask + up16(n), o_end = o_flags + (flags ? up16(n) : 0);
+    const hipError_t e = blk.reserve(ctx, (n_docs ? o_end : o_back) + 16);
+    if (e != hipSuccess) return e;
+    uint8_t* p = blk.p;
+    *w = MeWork{(uint32_t*)p, (uint32_t*)(p + o_counts), (uint64_t*)(p + o_base), (uint32_t*)(p + o_local),
+                (uint64_t*)(p + o_bsum), (uint64_t*)(p + o_bsum) + nblk + 1, (uint64_t*)(p + o_slot),
+                (unsigned long long*)(p + o_back), nullptr, nullptr, nullptr};
+    if (n_docs) w->doc_written = (uint32_t*)(p + o_docw), w->mask = p + o_mask, w->flags = p + o_flags;
+    return hipSuccess;
+}
+
+// the heap arena for long_total bytes in long segments (none: no block) and the layout's slots
+hipError_t me_arena(gbpe_ctx* ctx, GbpeArray<uint8_t>& blk, uint64_t long_total, const uint64_t* slot, MeArena* ar) {
+    *ar = MeArena{};
+    ar->slot = slot;
+    if (!long_total) return hipSuccess;
+    const hipError_t e = blk.reserve(ctx, long_total * (3 * sizeof(uint32_t) + 3 * sizeof(uint64_t)) + 64);
+    if (e != hipSuccess) return e;
+    ar->heap = (uint64_t*)blk.p;
+    ar->tok = (uint32_t*)(ar->heap + 3 * long_total);
+    ar->nxt = ar->tok + long_total;
+    ar->prv = ar->nxt + long_total;
+    return hipSuccess;
+}
+
+struct MeDocJob {   // the documents of a batch call, n_docs > 0
+    const uint64_t* d_doc_off;   // [0, n_docs]
+    uint64_t n_docs;
+    uint64_t* d_tok_off;         // [0, n_docs]
+};
+
+// w.mask of a batch call: bit 0 = `the mode's per-document mask | document starts` (mode NONE:
+// document starts only), ME_DOC_BIT = a document starts here.  The first kernel checks the offsets
+// into the second word of w.back (zeroed by the caller).
+int me_docs_mask(gbpe_ctx* ctx, const uint8_t* d_in, uint64_t n, const uint8_t* d_ws, uint32_t mode, const MeDocJob& docs,
+                 const MeWork& w) {
     hipStream_t s = ctx->stream;
-    const bool words = mode != GBPE_WORDS_NONE;
+    uint32_t* d_invalid = (uint32_t*)(w.back + 1);
+    int rc = GBPE_OK;
+    if (mode == GBPE_WORDS_GPT4) {
+        GBPE_HIP(ctx, hipMemsetAsync(w.flags, 0, n, s));
+        rc = gbpe_doc_flags_launch(ctx, docs.d_doc_off, docs.n_docs, n, w.flags, 1u, d_invalid);
+        if (rc == GBPE_OK) rc = gbpe_pretok_gpt4_docs_launch(ctx, d_in, n, w.flags, w.mask);
+    } else {
+        rc = gbpe_doc_flags_launch(ctx, docs.d_doc_off, docs.n_docs, n, nullptr, 0u, d_invalid);
+        if (rc == GBPE_OK && mode == GBPE_WORDS_NONE) {
+            GBPE_HIP(ctx, hipMemsetAsync(w.mask, 0, n, s));
+        } else if (rc == GBPE_OK && mode == GBPE_WORDS_MASK) {
+            hipLaunchKernelGGL(k_me_mask01, dim3((uint32_t)gbpe_div_up(n, 1024)), dim3(256), 0, s, d_ws, n, w.mask);
+        } else if (rc == GBPE_OK) {
+            rc = gbpe_word_boundary_launch(ctx, d_in, n, w.mask);
+        }
+    }
+    if (rc == GBPE_OK) rc = gbpe_doc_flags_launch(ctx, docs.d_doc_off, docs.n_docs, n, w.mask, ME_DOC_BIT, nullptr);
+    return rc;
+}
+
+// d_in[0, n) (and, mode MASK, d_ws[0, n)) → d_out[0, min(total, out_cap)); n > 0, the mode checked.
+// With `docs`, also d_doc_off[0, n_docs] → d_tok_off[0, n_docs]: the tokens are the word kernels'
+// under me_docs_mask's mask.  The offsets' verdict comes back with the long-segment total, the
+// call's first synchronise, before anything is written to d_out or d_tok_off.  `what` names the
+// entry point in error texts.
+int me_run(gbpe_ctx* ctx, gbpe_bpe* bp, const char* what, const uint8_t* d_in, uint64_t n, const uint8_t* d_ws,
+           uint32_t mode, uint32_t* d_out, uint64_t out_cap, const MeDocJob* docs, uint64_t* n_out) {
+    hipStream_t s = ctx->stream;
+    const bool words = docs || mode != GBPE_WORDS_NONE;   // (a document start is a cut)
     uint32_t cs = ME_CS;
     if (words) {
         cs = (uint32_t)gbpe_debug_knob("me_cs", ME_CS_WORDS);   // (read per call: the bench and the tests run all three)
         if (cs != 4096u && cs != 1024u && cs != 256u)
             return gbpe_set_error(ctx, GBPE_E_INVALID, "GBPE_DEBUG me_cs: %u is not 4096, 1024 or 256", cs);
     }
-    const uint32_t lslot = me_lslot(cs);
     const uint64_t nchunks = gbpe_div_up(n, cs);
     const uint64_t nblk = gbpe_div_up(nchunks, SCAN_BLK);
-    // one pooled block: scratch tokens (<= 1 per byte), counts, bases, scan state, long-segment slots
-    const uint64_t o_counts = up16(4 * n), o_base = o_counts + up16(4 * nchunks), o_local = o_base + up16(8 * nchunks);
-    const uint64_t o_bsum = o_local + up16(4 * nchunks), o_slot = o_bsum + up16(8 * (nblk + 2));
-    const uint64_t o_long = o_slot + up16(8 * nchunks * lslot);
     GbpeArray<uint8_t> work, mask, arena;
-    GBPE_HIP(ctx, work.reserve(ctx, o_long + 16));
-    uint32_t* scratch = (uint32_t*)work.p;
-    uint32_t* counts = (uint32_t*)(work.p + o_counts);
-    uint64_t* base = (uint64_t*)(work.p + o_base);
-    uint32_t* local = (uint32_t*)(work.p + o_local);
-    uint64_t* blocksum = (uint64_t*)(work.p + o_bsum);
-    uint64_t* total = blocksum + nblk + 1;
-    uint64_t* slot = (uint64_t*)(work.p + o_slot);
-    unsigned long long* d_long = (unsigned long long*)(work.p + o_long);
-    MeTable t{bp->slots, bp->mask, bp->cross};
+    MeWork w;
+    GBPE_HIP(ctx, me_layout(ctx, work, n, cs, nchunks, nblk, docs ? docs->n_docs : 0, docs && mode == GBPE_WORDS_GPT4, &w));
+    const MeTable t{bp->slots, bp->mask, bp->cross};
+    const uint64_t cell = docs ? 16 : 8;   // of w.back: a batch call also reads the offsets' verdict
 
     GBPE_HIP(ctx, hipEventRecord(ctx->ev[0], s));
-    if (mode == GBPE_WORDS_HEURISTIC || mode == GBPE_WORDS_GPT4) {
+    int rc = GBPE_OK;
+    if (docs) {
+        GBPE_HIP(ctx, hipMemsetAsync(w.back, 0, cell, s));
+        rc = me_docs_mask(ctx, d_in, n, d_ws, mode, *docs, w);
+        d_ws = w.mask;
+    } else if (mode == GBPE_WORDS_HEURISTIC || mode == GBPE_WORDS_GPT4) {
         GBPE_HIP(ctx, mask.reserve(ctx, n));
-        const int rc = mode == GBPE_WORDS_GPT4 ? gbpe_pretok_gpt4_launch(ctx, d_in, n, mask.p)
-                                               : gbpe_word_boundary_launch(ctx, d_in, n, mask.p);
-        if (rc != GBPE_OK) {
-            hipStreamSynchronize(s);   // (the mask block goes back to the pool)
-            return rc;
-        }
+        rc = mode == GBPE_WORDS_GPT4 ? gbpe_pretok_gpt4_launch(ctx, d_in, n, mask.p)
+                                     : gbpe_word_boundary_launch(ctx, d_in, n, mask.p);
         d_ws = mask.p;
+    }
+    if (rc != GBPE_OK) {
+        hipStreamSynchronize(s);   // (the pooled blocks are given back on return)
+        return rc;
     }
     GBPE_HIP(ctx, hipEventRecord(ctx->ev[1], s));
     // long segments: their total length sizes the heap arena (none: no arena)
-    hipError_t e = hipMemsetAsync(d_long, 0, 8, s);
+    hipError_t e = docs ? hipSuccess : hipMemsetAsync(w.back, 0, cell, s);
     if (e == hipSuccess) {
-        ME_DISPATCH(me_launch_long, words, cs, s, d_in, d_ws, n, t, d_long, slot, nchunks);
+        ME_DISPATCH(me_launch_long, words, cs, s, d_in, d_ws, n, t, w.back, w.slot, nchunks);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipEventRecord(ctx->ev[2], s);
-    if (e == hipSuccess) e = hipMemcpyAsync(ctx->enc_host_total, d_long, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    uint64_t long_total = 0;
-    memcpy(&long_total, ctx->enc_host_total, 8);
+    if (e == hipSuccess) e = hipMemcpyAsync(ctx->enc_host_total, w.back, cell, hipMemcpyDeviceToHost, s);
+    const hipError_t e1 = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = e1;
+    uint64_t back[2] = {0, 0};   // {long-segment total, bad offsets}
+    memcpy(back, ctx->enc_host_total, cell);
+    if (e == hipSuccess && (uint32_t)back[1]) return gbpe_doc_offsets_error(ctx, what, (uint32_t)back[1]);   // nothing was written
     MeArena ar{};
-    ar.slot = slot;
-    if (e == hipSuccess && long_total) {
-        e = arena.reserve(ctx, long_total * (3 * sizeof(uint32_t) + 3 * sizeof(uint64_t)) + 64);
-        if (e == hipSuccess) {
-            ar.heap = (uint64_t*)arena.p;
-            ar.tok = (uint32_t*)(ar.heap + 3 * long_total);
-            ar.nxt = ar.tok + long_total;
-            ar.prv = ar.nxt + long_total;
-        }
-    }
+    if (e == hipSuccess) e = me_arena(ctx, arena, back[0], w.slot, &ar);
     if (e == hipSuccess) e = hipEventRecord(ctx->ev[3], s);
     if (e == hipSuccess) {
-        ME_DISPATCH(me_launch_walk, words, cs, s, d_in, d_ws, n, t, scratch, counts, base, nchunks, ar);
+        const MeDocs md{docs ? docs->d_doc_off : nullptr, docs ? docs->n_docs : 0, w.doc_written};
+        ME_DISPATCH(me_launch_walk, words, cs, s, d_in, d_ws, n, t, w.scratch, w.counts, w.base, nchunks, ar,
+                    docs ? &md : nullptr);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipEventRecord(ctx->ev[4], s);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_chunk_scan1, dim3((uint32_t)nblk), dim3(SCAN_TPB), 0, s, (const uint32_t*)counts, nchunks,
-                           local, blocksum);
-        hipLaunchKernelGGL(k_chunk_scan2, dim3(1), dim3(SCAN_TPB), 0, s, blocksum, nblk, total);
+        hipLaunchKernelGGL(k_chunk_scan1, dim3((uint32_t)nblk), dim3(SCAN_TPB), 0, s, (const uint32_t*)w.counts, nchunks,
+                           w.local, w.blocksum);
+        hipLaunchKernelGGL(k_chunk_scan2, dim3(1), dim3(SCAN_TPB), 0, s, w.blocksum, nblk, w.total);
         if (out_cap)
             hipLaunchKernelGGL(k_me_compact, dim3((uint32_t)gbpe_div_up(nchunks, 4)), dim3(256), 0, s,
-                               (const uint32_t*)scratch, (const uint32_t*)counts, (const uint64_t*)base,
-                               (const uint32_t*)local, (const uint64_t*)blocksum, nchunks, d_out, out_cap);
+                               (const uint32_t*)w.scratch, (const uint32_t*)w.counts, (const uint64_t*)w.base,
+                               (const uint32_t*)w.local, (const uint64_t*)w.blocksum, nchunks, d_out, out_cap);
+        if (docs)   // (runs whether or not the tokens fit: tok_off is complete on GBPE_E_CAPACITY)
+            hipLaunchKernelGGL(k_me_tok_off, dim3((uint32_t)gbpe_div_up(docs->n_docs + 1, 256)), dim3(256), 0, s,
+                               docs->d_doc_off, docs->n_docs, n, cs, (const uint32_t*)w.doc_written,
+                               (const uint32_t*)w.local, (const uint64_t*)w.blocksum, (const uint64_t*)w.total,
+                               docs->d_tok_off);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipEventRecord(ctx->ev[5], s);
-    if (e == hipSuccess) e = hipMemcpyAsync(ctx->enc_host_total, total, 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(ctx->enc_host_total, w.total, 8, hipMemcpyDeviceToHost, s);
     const hipError_t es = hipStreamSynchronize(s);   // (always: the pooled blocks are given back on return)
     if (e == hipSuccess) e = es;
     if (e != hipSuccess)
-        return gbpe_set_error(ctx, e == hipErrorOutOfMemory ? GBPE_E_OOM : GBPE_E_DEVICE, "bpe encode (words) failed: %s",
+        return gbpe_set_error(ctx, e == hipErrorOutOfMemory ? GBPE_E_OOM : GBPE_E_DEVICE, "%s failed: %s", what,
                               hipGetErrorString(e));
     float a = 0, b = 0, c = 0, d = 0;
     hipEventElapsedTime(&a, ctx->ev[0], ctx->ev[1]);
@@ -633,7 +641,8 @@ int me_words_device(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* d_in, uint64_t n
     memcpy(&tot, ctx->enc_host_total, 8);
     *n_out = tot;
     if (tot > out_cap)
-        return gbpe_set_error(ctx, GBPE_E_CAPACITY, "bpe encode: output needs %llu tokens", (unsigned long long)tot);
+        return gbpe_set_error(ctx, GBPE_E_CAPACITY, "bpe encode%s: output needs %llu tokens", docs ? " batch" : "",
+                              (unsigned long long)tot);
     return GBPE_OK;
 }
 
@@ -656,8 +665,8 @@ extern "C" int gbpe_bpe_encode_words_device(gbpe_ctx* ctx, gbpe_bpe* bp, const v
     if (rc != GBPE_OK) return rc;
     if ((uintptr_t)d_out & 3u) return gbpe_set_error(ctx, GBPE_E_INVALID, "d_out must be 4-byte aligned");
     if (n == 0) return GBPE_OK;
-    return me_words_device(ctx, bp, (const uint8_t*)d_bytes, n, (const uint8_t*)d_word_starts, words_mode,
-                           (uint32_t*)d_out, out_cap, n_out);
+    return me_run(ctx, bp, "bpe encode (words)", (const uint8_t*)d_bytes, n, (const uint8_t*)d_word_starts, words_mode,
+                  (uint32_t*)d_out, out_cap, nullptr, n_out);
 }
 
 extern "C" int gbpe_bpe_encode_words(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* bytes, uint64_t n,
@@ -679,7 +688,7 @@ extern "C" int gbpe_bpe_encode_words(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t*
     hipError_t e = hipMemcpyAsync(io.p, bytes, n, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && word_starts) e = hipMemcpyAsync(d_ws, word_starts, n, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
-        rc = me_words_device(ctx, bp, io.p, n, d_ws, words_mode, (uint32_t*)(io.p + o_out), cap, n_out);
+        rc = me_run(ctx, bp, "bpe encode (words)", io.p, n, d_ws, words_mode, (uint32_t*)(io.p + o_out), cap, nullptr, n_out);
         if (rc != GBPE_OK && rc != GBPE_E_CAPACITY) return rc;   // (synchronised there)
         const uint64_t fit = *n_out < cap ? *n_out : cap;
         if (fit) e = hipMemcpyAsync(out, io.p + o_out, fit * 4, hipMemcpyDeviceToHost, s);
@@ -690,148 +699,13 @@ extern "C" int gbpe_bpe_encode_words(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t*
     return rc;
 }
 
+// the whole string: no word cuts (the words contract, gpubpe.h)
+extern "C" int gbpe_bpe_encode(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* bytes, uint64_t n, uint32_t* out,
+                               uint64_t out_cap, uint64_t* n_out) {
+    return gbpe_bpe_encode_words(ctx, bp, bytes, n, nullptr, GBPE_WORDS_NONE, out, out_cap, n_out);
+}
+
 // ── many documents in one call (gbpe_bpe_encode_words_batch*) ──
-
-namespace {
-
-template <uint32_t CS>
-void me_launch_walk_docs(hipStream_t s, const uint8_t* in, const uint8_t* ws, uint64_t n, const MeTable& t,
-                         uint32_t* scratch, uint32_t* counts, uint64_t* base, uint64_t nchunks, const MeArena& ar,
-                         const MeDocs& docs) {
-    hipLaunchKernelGGL((k_me_walk_docs<CS>), dim3((uint32_t)gbpe_div_up(nchunks, ME_TPB)), dim3(ME_TPB), 0, s, in, ws, n, t,
-                       scratch, counts, base, nchunks, ar, docs);
-}
-
-// d_in[0, n), d_doc_off[0, n_docs] (and, mode MASK, d_ws[0, n)) → d_out[0, min(total, out_cap)) and
-// d_tok_off[0, n_docs]; n, n_docs > 0, the mode checked.  The tokens are the word kernels' under the
-// mask `the mode's per-document mask | document starts` (mode NONE: document starts only).  The
-// offsets are checked by the first kernel; what it found comes back with the long-segment total, the
-// call's first synchronise, before anything is written to d_out or d_tok_off.
-int me_words_batch_device(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* d_in, uint64_t n, const uint64_t* d_doc_off,
-                          uint64_t n_docs, const uint8_t* d_ws, uint32_t mode, uint32_t* d_out, uint64_t out_cap,
-                          uint64_t* d_tok_off, uint64_t* n_out) {
-    hipStream_t s = ctx->stream;
-    const uint32_t cs = (uint32_t)gbpe_debug_knob("me_cs", ME_CS_WORDS);
-    if (cs != 4096u && cs != 1024u && cs != 256u)
-        return gbpe_set_error(ctx, GBPE_E_INVALID, "GBPE_DEBUG me_cs: %u is not 4096, 1024 or 256", cs);
-    const uint32_t lslot = me_lslot(cs);
-    const uint64_t nchunks = gbpe_div_up(n, cs);
-    const uint64_t nblk = gbpe_div_up(nchunks, SCAN_BLK);
-    // one pooled block: me_words_device's, then the per-document counts, the mask and (GPT-4) the flags
-    const uint64_t o_counts = up16(4 * n), o_base = o_counts + up16(4 * nchunks), o_local = o_base + up16(8 * nchunks);
-    const uint64_t o_bsum = o_local + up16(4 * nchunks), o_slot = o_bsum + up16(8 * (nblk + 2));
-    const uint64_t o_long = o_slot + up16(8 * nchunks * lslot), o_docw = o_long + 16, o_mask = o_docw + up16(4 * n_docs);
-    const uint64_t o_flags = o_mask + up16(n), o_end = o_flags + (mode == GBPE_WORDS_GPT4 ? up16(n) : 0);
-    GbpeArray<uint8_t> work, arena;
-    GBPE_HIP(ctx, work.reserve(ctx, o_end + 16));
-    uint32_t* scratch = (uint32_t*)work.p;
-    uint32_t* counts = (uint32_t*)(work.p + o_counts);
-    uint64_t* base = (uint64_t*)(work.p + o_base);
-    uint32_t* local = (uint32_t*)(work.p + o_local);
-    uint64_t* blocksum = (uint64_t*)(work.p + o_bsum);
-    uint64_t* total = blocksum + nblk + 1;
-    uint64_t* slot = (uint64_t*)(work.p + o_slot);
-    unsigned long long* d_long = (unsigned long long*)(work.p + o_long);
-    uint32_t* d_invalid = (uint32_t*)(work.p + o_long + 8);
-    uint32_t* doc_written = (uint32_t*)(work.p + o_docw);
-    uint8_t* m = work.p + o_mask;
-    uint8_t* flags = work.p + o_flags;
-    MeTable t{bp->slots, bp->mask, bp->cross};
-
-    GBPE_HIP(ctx, hipEventRecord(ctx->ev[0], s));
-    GBPE_HIP(ctx, hipMemsetAsync(d_long, 0, 16, s));
-    int rc = GBPE_OK;
-    if (mode == GBPE_WORDS_GPT4) {
-        GBPE_HIP(ctx, hipMemsetAsync(flags, 0, n, s));
-        rc = gbpe_doc_flags_launch(ctx, d_doc_off, n_docs, n, flags, 1u, d_invalid);
-        if (rc == GBPE_OK) rc = gbpe_pretok_gpt4_docs_launch(ctx, d_in, n, flags, m);
-        if (rc == GBPE_OK) rc = gbpe_doc_flags_launch(ctx, d_doc_off, n_docs, n, m, ME_DOC_BIT, nullptr);
-    } else {
-        rc = gbpe_doc_flags_launch(ctx, d_doc_off, n_docs, n, nullptr, 0u, d_invalid);
-        if (rc == GBPE_OK && mode == GBPE_WORDS_NONE) {
-            GBPE_HIP(ctx, hipMemsetAsync(m, 0, n, s));
-        } else if (rc == GBPE_OK && mode == GBPE_WORDS_MASK) {
-            hipLaunchKernelGGL(k_me_mask01, dim3((uint32_t)gbpe_div_up(n, 1024)), dim3(256), 0, s, d_ws, n, m);
-        } else if (rc == GBPE_OK) {
-            rc = gbpe_word_boundary_launch(ctx, d_in, n, m);
-        }
-        if (rc == GBPE_OK) rc = gbpe_doc_flags_launch(ctx, d_doc_off, n_docs, n, m, ME_DOC_BIT, nullptr);
-    }
-    if (rc != GBPE_OK) {
-        hipStreamSynchronize(s);   // (the work block goes back to the pool)
-        return rc;
-    }
-    GBPE_HIP(ctx, hipEventRecord(ctx->ev[1], s));
-    // long segments: their total length sizes the heap arena (none: no arena)
-    ME_DISPATCH(me_launch_long, true, cs, s, d_in, (const uint8_t*)m, n, t, d_long, slot, nchunks);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipEventRecord(ctx->ev[2], s);
-    if (e == hipSuccess) e = hipMemcpyAsync(ctx->enc_host_total, d_long, 16, hipMemcpyDeviceToHost, s);
-    const hipError_t e1 = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = e1;
-    uint64_t long_total = 0;
-    uint32_t bad = 0;
-    memcpy(&long_total, ctx->enc_host_total, 8);
-    memcpy(&bad, (const uint8_t*)ctx->enc_host_total + 8, 4);
-    if (e == hipSuccess && bad) return gbpe_doc_offsets_error(ctx, "bpe encode batch", bad);   // nothing was written
-    MeArena ar{};
-    ar.slot = slot;
-    if (e == hipSuccess && long_total) {
-        e = arena.reserve(ctx, long_total * (3 * sizeof(uint32_t) + 3 * sizeof(uint64_t)) + 64);
-        if (e == hipSuccess) {
-            ar.heap = (uint64_t*)arena.p;
-            ar.tok = (uint32_t*)(ar.heap + 3 * long_total);
-            ar.nxt = ar.tok + long_total;
-            ar.prv = ar.nxt + long_total;
-        }
-    }
-    if (e == hipSuccess) e = hipEventRecord(ctx->ev[3], s);
-    if (e == hipSuccess) {
-        const MeDocs docs{d_doc_off, n_docs, doc_written};
-        if (cs == 4096u) me_launch_walk_docs<4096u>(s, d_in, m, n, t, scratch, counts, base, nchunks, ar, docs);
-        else if (cs == 1024u) me_launch_walk_docs<1024u>(s, d_in, m, n, t, scratch, counts, base, nchunks, ar, docs);
-        else me_launch_walk_docs<256u>(s, d_in, m, n, t, scratch, counts, base, nchunks, ar, docs);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(ctx->ev[4], s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_chunk_scan1, dim3((uint32_t)nblk), dim3(SCAN_TPB), 0, s, (const uint32_t*)counts, nchunks,
-                           local, blocksum);
-        hipLaunchKernelGGL(k_chunk_scan2, dim3(1), dim3(SCAN_TPB), 0, s, blocksum, nblk, total);
-        if (out_cap)
-            hipLaunchKernelGGL(k_me_compact, dim3((uint32_t)gbpe_div_up(nchunks, 4)), dim3(256), 0, s,
-                               (const uint32_t*)scratch, (const uint32_t*)counts, (const uint64_t*)base,
-                               (const uint32_t*)local, (const uint64_t*)blocksum, nchunks, d_out, out_cap);
-        // (runs whether or not the tokens fit: tok_off is complete on GBPE_E_CAPACITY)
-        hipLaunchKernelGGL(k_me_tok_off, dim3((uint32_t)gbpe_div_up(n_docs + 1, 256)), dim3(256), 0, s, d_doc_off, n_docs, n,
-                           cs, (const uint32_t*)doc_written, (const uint32_t*)local, (const uint64_t*)blocksum,
-                           (const uint64_t*)total, d_tok_off);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(ctx->ev[5], s);
-    if (e == hipSuccess) e = hipMemcpyAsync(ctx->enc_host_total, total, 8, hipMemcpyDeviceToHost, s);
-    const hipError_t es = hipStreamSynchronize(s);   // (always: the pooled blocks are given back on return)
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess)
-        return gbpe_set_error(ctx, e == hipErrorOutOfMemory ? GBPE_E_OOM : GBPE_E_DEVICE, "bpe encode batch failed: %s",
-                              hipGetErrorString(e));
-    float a = 0, b = 0, c = 0, d = 0;
-    hipEventElapsedTime(&a, ctx->ev[0], ctx->ev[1]);
-    hipEventElapsedTime(&b, ctx->ev[1], ctx->ev[2]);
-    hipEventElapsedTime(&c, ctx->ev[3], ctx->ev[4]);
-    hipEventElapsedTime(&d, ctx->ev[4], ctx->ev[5]);
-    ctx->bpe_ms[0] = a;
-    ctx->bpe_ms[1] = (double)b + c;
-    ctx->bpe_ms[2] = d;
-    uint64_t tot = 0;
-    memcpy(&tot, ctx->enc_host_total, 8);
-    *n_out = tot;
-    if (tot > out_cap)
-        return gbpe_set_error(ctx, GBPE_E_CAPACITY, "bpe encode batch: output needs %llu tokens", (unsigned long long)tot);
-    return GBPE_OK;
-}
-
-}  // namespace
 
 extern "C" int gbpe_bpe_encode_words_batch_device(gbpe_ctx* ctx, gbpe_bpe* bp, const void* d_bytes, uint64_t n,
                                                   const void* d_doc_off, uint64_t n_docs, const void* d_word_starts,
@@ -850,9 +724,9 @@ extern "C" int gbpe_bpe_encode_words_batch_device(gbpe_ctx* ctx, gbpe_bpe* bp, c
         GBPE_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return GBPE_OK;
     }
-    return me_words_batch_device(ctx, bp, (const uint8_t*)d_bytes, n, (const uint64_t*)d_doc_off, n_docs,
-                                 (const uint8_t*)d_word_starts, words_mode, (uint32_t*)d_out, out_cap, (uint64_t*)d_tok_off,
-                                 n_out);
+    const MeDocJob docs{(const uint64_t*)d_doc_off, n_docs, (uint64_t*)d_tok_off};
+    return me_run(ctx, bp, "bpe encode batch", (const uint8_t*)d_bytes, n, (const uint8_t*)d_word_starts, words_mode,
+                  (uint32_t*)d_out, out_cap, &docs, n_out);
 }
 
 extern "C" int gbpe_bpe_encode_words_batch(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* bytes, uint64_t n,
@@ -882,8 +756,9 @@ extern "C" int gbpe_bpe_encode_words_batch(gbpe_ctx* ctx, gbpe_bpe* bp, const ui
     if (e == hipSuccess) e = hipMemcpyAsync(io.p + o_in, bytes, n, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && word_starts) e = hipMemcpyAsync(d_ws, word_starts, n, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
-        rc = me_words_batch_device(ctx, bp, io.p + o_in, n, (const uint64_t*)io.p, n_docs, d_ws, words_mode,
-                                   (uint32_t*)(io.p + o_out), cap, (uint64_t*)(io.p + o_tok), n_out);
+        const MeDocJob docs{(const uint64_t*)io.p, n_docs, (uint64_t*)(io.p + o_tok)};
+        rc = me_run(ctx, bp, "bpe encode batch", io.p + o_in, n, d_ws, words_mode, (uint32_t*)(io.p + o_out), cap, &docs,
+                    n_out);
         if (rc != GBPE_OK && rc != GBPE_E_CAPACITY) return rc;   // (synchronised there)
         e = hipMemcpyAsync(tok_off, io.p + o_tok, 8 * (n_docs + 1), hipMemcpyDeviceToHost, s);
         const uint64_t fit = *n_out < cap ? *n_out : cap;

@@ -569,18 +569,8 @@ int pretok_launch(gbpe_ctx* ctx, const uint8_t* d_bytes, uint64_t n, const uint8
     if (rc != GBPE_OK) return rc;
     hipStream_t s = ctx->stream;
     const uint64_t nblk = gbpe_div_up(n, PT_BLK);
-    const uint64_t need = (nblk + 1) * sizeof(uint32_t);
-    if (ctx->pt_agg_bytes < need) {   // per-context pool: grows, never shrinks
-        if (ctx->pt_agg) {
-            GBPE_HIP(ctx, hipStreamSynchronize(s));
-            GBPE_HIP(ctx, hipFree(ctx->pt_agg));
-            ctx->pt_agg = nullptr;
-            ctx->pt_agg_bytes = 0;
-        }
-        GBPE_HIP(ctx, dev_malloc(ctx, &ctx->pt_agg, need + need / 2));
-        ctx->pt_agg_bytes = need + need / 2;
-    }
-    uint32_t* agg = (uint32_t*)ctx->pt_agg;
+    GBPE_HIP(ctx, ctx->pt_agg.reserve(ctx, (nblk + 1) * sizeof(uint32_t)));
+    uint32_t* agg = (uint32_t*)ctx->pt_agg.p;
     if (d_flags) {
         hipLaunchKernelGGL(k_pt_scan1_docs, dim3((uint32_t)nblk), dim3(PT_TPB), 0, s, d_bytes, n, d_flags, idx, cls, agg);
         hipLaunchKernelGGL(k_pt_scan2, dim3(1), dim3(1024), 0, s, agg, nblk);
@@ -640,14 +630,14 @@ extern "C" int gbpe_pretokenize_gpt4(gbpe_ctx* ctx, const uint8_t* bytes, uint64
     if (!ctx || (n && (!bytes || !ws_out))) return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
     if (n == 0) return GBPE_OK;
     hipStream_t s = ctx->stream;
-    uint8_t* d = nullptr;
-    GBPE_HIP(ctx, dev_malloc(ctx, &d, 2 * n));
-    hipError_t e = hipMemcpyAsync(d, bytes, n, hipMemcpyHostToDevice, s);
-    int rc = e == hipSuccess ? gbpe_pretok_gpt4_launch(ctx, d, n, d + n) : GBPE_E_DEVICE;
-    if (rc == GBPE_OK) e = hipMemcpyAsync(ws_out, d + n, n, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    hipFree(d);
-    if (rc != GBPE_OK) return rc;
+    GbpeArray<uint8_t> io;   // one pooled block: bytes, mask
+    GBPE_HIP(ctx, io.reserve(ctx, 2 * n));
+    hipError_t e = hipMemcpyAsync(io.p, bytes, n, hipMemcpyHostToDevice, s);
+    const int rc = e == hipSuccess ? gbpe_pretok_gpt4_launch(ctx, io.p, n, io.p + n) : GBPE_OK;
+    if (e == hipSuccess && rc == GBPE_OK) e = hipMemcpyAsync(ws_out, io.p + n, n, hipMemcpyDeviceToHost, s);
+    const hipError_t es = hipStreamSynchronize(s);   // (always: the block goes back to the pool on return)
+    if (e == hipSuccess) e = es;
+    if (rc != GBPE_OK) return rc;   // (its message is set)
     if (e != hipSuccess) return gbpe_set_error(ctx, GBPE_E_DEVICE, "pretokenize failed: %s", hipGetErrorString(e));
     return GBPE_OK;
 }

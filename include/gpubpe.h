@@ -375,7 +375,12 @@ int gbpe_encode_batch_device(gbpe_ctx* ctx, gbpe_trie* trie, const void* d_bytes
                              uint64_t* n_out);
 /* ── merge-rank encode: TokenizerManager.encode (tokenizer-manager.js:13-61) ──
  * merges = [a, b, newId] x n in learned order.  Exact for any merge list: a
- * merge whose operand is only created later never fires (as in the reference). */
+ * merge whose operand is only created later never fires (as in the reference).
+ * gbpe_bpe_encode is gbpe_bpe_encode_words (below) with GBPE_WORDS_NONE and no
+ * mask, and has its contract: on GBPE_E_CAPACITY *n_out holds the required token
+ * count and the first out_cap tokens are in place; out == NULL goes with
+ * out_cap == 0 only (the size query), else GBPE_E_INVALID.
+ * gbpe_bpe_encode_last_timing reports this call too. */
 typedef struct gbpe_bpe gbpe_bpe;
 int  gbpe_bpe_upload(gbpe_ctx* ctx, const uint32_t* merges, uint32_t n_merges, gbpe_bpe** out);
 int  gbpe_bpe_encode(gbpe_ctx* ctx, gbpe_bpe* bpe, const uint8_t* bytes, uint64_t n, uint32_t* out, uint64_t out_cap,

@@ -306,6 +306,39 @@ def test_whole_string_encode_unchanged(engine):
         enc.destroy()
 
 
+def plain_call(engine, enc, data, out_cap, null_out=False):
+    """gbpe_bpe_encode into a guarded host array (or out = NULL): (status, n_out, out[out_cap + GUARD])."""
+    out = np.full(out_cap + GUARD, CANARY, np.uint32)
+    buf = C.create_string_buffer(data, len(data)) if data else None
+    n = C.c_uint64(12345)
+    outp = None if null_out else out.ctypes.data_as(_lib.u32p)
+    rc = _lib.load().gbpe_bpe_encode(engine.device, enc._h, buf, len(data), outp, out_cap, C.byref(n))
+    return rc, int(n.value), out
+
+
+@pytest.mark.parametrize("data", [b"aaaa aaaaa", b"a" * 1025 + b" aa"], ids=["short", "long-segment"])
+def test_whole_string_encode_statuses(engine, enc_a, data):
+    # gbpe_bpe_encode is gbpe_bpe_encode_words with GBPE_WORDS_NONE: its statuses and its tokens
+    # (the second input has one segment just past 1024 bytes: the heap arena path)
+    want = O.encode_merge_order(data, A_MERGES)
+    total = len(want)
+    rc, n, out = plain_call(engine, enc_a, data, total)
+    assert rc == _lib.GBPE_OK and n == total and out[:total].tolist() == want and (out[total:] == CANARY).all()
+    wrc, wn, wout = host_call(engine, enc_a, data, None, NONE, out_cap=total)
+    assert (wrc, wn) == (rc, n) and (wout == out).all()
+    rc, n, out = plain_call(engine, enc_a, data, total - 1)
+    assert rc == _lib.GBPE_E_CAPACITY and n == total
+    assert out[: total - 1].tolist() == want[: total - 1] and (out[total - 1:] == CANARY).all()
+    wrc, wn, wout = host_call(engine, enc_a, data, None, NONE, out_cap=total - 1)
+    assert (wrc, wn) == (rc, n) and (wout == out).all()
+    rc, n, out = plain_call(engine, enc_a, data, 0, null_out=True)
+    assert rc == _lib.GBPE_E_CAPACITY and n == total and (out == CANARY).all()
+    rc, n, out = plain_call(engine, enc_a, b"", 4)
+    assert rc == _lib.GBPE_OK and n == 0 and (out == CANARY).all()
+    wrc, wn, wout = host_call(engine, enc_a, b"", None, NONE, out_cap=4)
+    assert (wrc, wn) == (rc, n) and (wout == out).all()
+
+
 # ── inventory and timing ───────────────────────────────────────────────────
 
 def test_inventory_and_timing(engine, enc_a):
