@@ -52,6 +52,11 @@ static const char* const kKernelNames[] = {
     "k_me_mask01",            // the caller's mask as 0 / 1 (bit 1 of a mask byte marks a document start)
     "k_me_walk_docs",         // k_me_walk_docs<CS>: the word walk + tokens written before each document start
     "k_me_tok_off",           // per-document token offsets
+    // special tokens of the merge-rank encode (gbpe_specials_mark*, gbpe_bpe_encode_special*)
+    "k_sp_cand",              // the longest special that matches at each byte
+    "k_sp_accept",            // the sequential scan's matches: a chain from every uncovered candidate
+    "k_me_sp_mask",           // the specials' spans and edges into the walk's mask
+    "k_me_walk_special",      // k_me_walk_docs<CS, true>: a special's span is one token
 };
 
 // ── context memory pool (common.h GbpePool) ───────────────────────────────

@@ -202,5 +202,12 @@ int gbpe_doc_flags_launch(gbpe_ctx* ctx, const uint64_t* d_doc_off, uint64_t n_d
                           uint32_t bit, uint32_t* d_invalid);
 int gbpe_doc_offsets_check(gbpe_ctx* ctx, const char* what, const uint64_t* doc_off, uint64_t n_docs, uint64_t n);   // host
 int gbpe_doc_offsets_error(gbpe_ctx* ctx, const char* what, uint32_t bad);
+// Special tokens (special.hip): d_mark[n] = 0 / 1 + index / 255 (gpubpe.h) of d_bytes[n] on
+// ctx->stream.  d_cand is n bytes of work, 16-byte aligned; d_doc_flags (nullptr: one document)
+// is non-zero where a document starts; d_flags (nullptr: none) gets 1 at byte 0, at each accepted
+// special's first byte and at the byte after its last: the pre-tokeniser's piece starts.
+int gbpe_specials_launch(gbpe_ctx* ctx, const gbpe_specials* sp, const uint8_t* d_bytes, uint64_t n,
+                         const uint8_t* d_doc_flags, uint8_t* d_cand, uint8_t* d_mark, uint8_t* d_flags);
+const uint32_t* gbpe_specials_ids(const gbpe_specials* sp);   // device: the ids in the caller's order
 // heuristic (byte-class) word starts of device bytes on ctx->stream (train.hip); any alignment
 int gbpe_word_boundary_launch(gbpe_ctx* ctx, const uint8_t* d_bytes, uint64_t n, uint8_t* d_ws);

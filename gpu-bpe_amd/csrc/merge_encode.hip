@@ -34,6 +34,11 @@
 // start is one more cut, so the tokens are the word walk's under the mask `the mode's
 // per-document mask | document starts`; k_me_walk_docs also notes how many tokens its
 // lane had written at each document start, and k_me_tok_off adds the chunk's prefix.
+//
+// Special tokens (gbpe_bpe_encode_special*): special.hip marks the accepted
+// matches; the mode's mask is built per piece between them (the GPT-4 rules through the
+// document form of the pre-tokeniser, a flag at each piece's first byte), k_me_sp_mask adds
+// the spans, and k_me_walk_docs<CS, true> writes a span's id as its one token.
 
 #include "common.h"
 #include "scan.h"
@@ -77,18 +82,41 @@ __device__ __forceinline__ uint4 me_find(const MeTable& t, uint32_t pid) {
     return make_uint4(0u, ME_NONE, 0u, 0u);
 }
 
-// a segment starts at byte i: a word start (WORDS), or no merge crosses (i - 1, i)
-template <bool WORDS>
+// Bits of a mask byte the library builds itself (a batch call, a call with special tokens): bit 0
+// a word start, ME_DOC_BIT a document start, ME_SP_BIT the first byte of an accepted
+// special token, ME_SPIN_BIT its other bytes.
+constexpr uint32_t ME_DOC_BIT = 2u, ME_SP_BIT = 4u, ME_SPIN_BIT = 8u;
+
+// a segment starts at byte i: a word start (WORDS), or no merge crosses (i - 1, i).  SP: never
+// inside a special, whatever the pair says — a lane whose chunk begins there must skip to its end
+template <bool WORDS, bool SP = false>
 __device__ __forceinline__ bool me_cut(const uint8_t* __restrict__ in, const uint8_t* __restrict__ ws, const MeTable& t,
                                        uint64_t i) {
     if (i == 0) return true;
-    if (WORDS && ws[i] != 0) return true;
+    if (SP) {
+        const uint32_t w = ws[i];
+        if (w) return w != ME_SPIN_BIT;   // (k_me_sp_mask leaves that bit alone on a span's inner bytes)
+    } else if (WORDS && ws[i] != 0) {
+        return true;
+    }
     const uint32_t k = ((uint32_t)in[i - 1] << 8) | in[i];
     return ((t.cross[k >> 5] >> (k & 31u)) & 1u) == 0u;
 }
 
-// the long segments (> ME_LONG bytes) starting in each chunk: arena offsets
-template <bool WORDS, uint32_t CS>
+// me_cut<true, true> that hands back the mask byte it read: the walk tests the byte of a segment's
+// start without loading it again
+__device__ __forceinline__ bool me_cut_sp(const uint8_t* __restrict__ in, const uint8_t* __restrict__ ws, const MeTable& t,
+                                          uint64_t i, uint32_t* w) {
+    *w = ws[i];
+    if (i == 0) return true;
+    if (*w) return *w != ME_SPIN_BIT;
+    const uint32_t k = ((uint32_t)in[i - 1] << 8) | in[i];
+    return ((t.cross[k >> 5] >> (k & 31u)) & 1u) == 0u;
+}
+
+// the long segments (> ME_LONG bytes) starting in each chunk: arena offsets (a special's span is a
+// segment of at most 128 bytes: never long)
+template <bool WORDS, uint32_t CS, bool SP = false>
 __global__ __launch_bounds__(ME_TPB) void k_me_long(const uint8_t* __restrict__ in, const uint8_t* __restrict__ ws,
                                                     uint64_t n, MeTable t, unsigned long long* __restrict__ total,
                                                     uint64_t* __restrict__ slot, uint64_t nchunks) {
@@ -96,11 +124,11 @@ __global__ __launch_bounds__(ME_TPB) void k_me_long(const uint8_t* __restrict__ 
     if (c >= nchunks) return;
     const uint64_t lo = c * CS, hi = min(lo + CS, n);
     uint64_t s = lo;
-    while (s < hi && !me_cut<WORDS>(in, ws, t, s)) ++s;
+    while (s < hi && !me_cut<WORDS, SP>(in, ws, t, s)) ++s;
     uint32_t k = 0;
     while (s < hi) {
         uint64_t z = s + 1;
-        while (z < n && !me_cut<WORDS>(in, ws, t, z)) ++z;
+        while (z < n && !me_cut<WORDS, SP>(in, ws, t, z)) ++z;
         if (z - s > ME_LONG) slot[c * me_lslot(CS) + k++] = atomicAdd(total, (unsigned long long)(z - s));
         s = z;
     }
@@ -247,27 +275,50 @@ struct MeDocs {
     uint64_t n_docs;
     uint32_t* written;
 };
-constexpr uint32_t ME_DOC_BIT = 2u;
+struct MeSp {   // the special tokens of a call (SP)
+    const uint8_t* mark;   // gbpe_specials_mark's array
+    const uint32_t* ids;   // by index
+};
 
-// k_me_walk<true, CS> + the tokens written before each document start
-template <uint32_t CS>
+// k_me_walk<true, CS> + the tokens written before each document start.  SP: a segment that begins
+// with ME_SP_BIT is a special's span (its other bytes are no cut, the byte after it is one): its id
+// is the segment's one token.  It belongs to the chunk that holds its first byte, and one token for
+// at least one byte keeps the tokens of a chunk behind the bytes it has consumed.
+template <uint32_t CS, bool SP = false>
 __global__ __launch_bounds__(ME_TPB) void k_me_walk_docs(const uint8_t* __restrict__ in, const uint8_t* __restrict__ ws,
                                                          uint64_t n, MeTable t, uint32_t* __restrict__ scratch,
                                                          uint32_t* __restrict__ counts, uint64_t* __restrict__ base,
-                                                         uint64_t nchunks, MeArena ar, MeDocs docs) {
+                                                         uint64_t nchunks, MeArena ar, MeDocs docs, MeSp sp) {
     const uint64_t c = (uint64_t)blockIdx.x * ME_TPB + threadIdx.x;
     if (c >= nchunks) return;
     const uint64_t lo = c * CS, hi = min(lo + CS, n);
     uint64_t s = lo;
-    while (s < hi && !me_cut<true>(in, ws, t, s)) ++s;   // first segment start in the chunk
+    uint32_t ws_s = 0, ws_z = 0;   // (SP) the mask bytes at s and at z
+    if constexpr (SP) {
+        while (s < hi && !me_cut_sp(in, ws, t, s, &ws_s)) ++s;
+    } else {
+        while (s < hi && !me_cut<true>(in, ws, t, s)) ++s;   // first segment start in the chunk
+    }
     base[c] = s;
     const uint64_t b0 = s;   // this chunk's tokens go to scratch[b0 ...]: never past the bytes consumed
     uint32_t written = 0, nlong = 0;
     while (s < hi) {
         uint64_t z = s + 1;
-        while (z < n && !me_cut<true>(in, ws, t, z)) ++z;   // the segment [s, z) may run past hi
-        if (ws[s] & ME_DOC_BIT) docs.written[me_first_doc(docs.doc_off, docs.n_docs, s)] = written;
+        if constexpr (SP) {
+            while (z < n && !me_cut_sp(in, ws, t, z, &ws_z)) ++z;
+        } else {
+            while (z < n && !me_cut<true>(in, ws, t, z)) ++z;   // the segment [s, z) may run past hi
+        }
+        const uint32_t w0 = SP ? ws_s : ws[s];
+        ws_s = ws_z;   // (z == n: not read, and the loop ends)
+        if (w0 & ME_DOC_BIT) docs.written[me_first_doc(docs.doc_off, docs.n_docs, s)] = written;
         uint32_t* tok = scratch + b0 + written;
+        if (SP && (w0 & ME_SP_BIT)) {
+            tok[0] = sp.ids[sp.mark[s] - 1u];
+            ++written;
+            s = z;
+            continue;
+        }
         uint32_t len = (uint32_t)(z - s);
         if (len > ME_LONG) {
             const uint64_t off = ar.slot[c * me_lslot(CS) + nlong++];
@@ -311,6 +362,43 @@ __global__ __launch_bounds__(256) void k_me_mask01(const uint8_t* __restrict__ w
         *reinterpret_cast<uint32_t*>(m + i) = v;   // (m is a pooled block: aligned)
     } else {
         for (uint64_t j = i; j < n; ++j) m[j] = ws[j] != 0;
+    }
+}
+
+// The accepted specials into the mode's 0 / 1 mask, 16 bytes per lane: a special's
+// first byte becomes `word start | ME_SP_BIT`, its other bytes ME_SPIN_BIT alone (whatever the
+// mode's mask held under the span goes), and the byte after its last is a word start.  Runs
+// before the document starts are ORed in; mark and m are pooled blocks (16-byte aligned).
+__global__ __launch_bounds__(256) void k_me_sp_mask(const uint8_t* __restrict__ mark, uint64_t n, uint8_t* __restrict__ m) {
+    const uint64_t i0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 16;
+    if (i0 >= n) return;
+    uint32_t prev = i0 ? mark[i0 - 1] : 0u;
+    if (i0 + 16 <= n) {
+        const uint4 kv = *reinterpret_cast<const uint4*>(mark + i0);
+        const uint32_t k4[4] = {kv.x, kv.y, kv.z, kv.w};
+        if ((kv.x | kv.y | kv.z | kv.w | prev) == 0u) return;   // no special here: the mask stands
+        const uint4 mv = *reinterpret_cast<const uint4*>(m + i0);
+        uint32_t m4[4] = {mv.x, mv.y, mv.z, mv.w};
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const uint32_t sh = 8 * (k & 3);
+            const uint32_t mk = (k4[k / 4] >> sh) & 0xFFu;
+            uint32_t v = (m4[k / 4] >> sh) & 0xFFu;
+            if (mk == 255u) v = ME_SPIN_BIT;
+            else if (mk) v = 1u | ME_SP_BIT;
+            else if (prev) v |= 1u;
+            m4[k / 4] = (m4[k / 4] & ~(0xFFu << sh)) | (v << sh);
+            prev = mk;
+        }
+        *reinterpret_cast<uint4*>(m + i0) = make_uint4(m4[0], m4[1], m4[2], m4[3]);
+    } else {
+        for (uint64_t i = i0; i < n; ++i) {
+            const uint32_t mk = mark[i];
+            if (mk == 255u) m[i] = ME_SPIN_BIT;
+            else if (mk) m[i] = 1u | ME_SP_BIT;
+            else if (prev) m[i] |= 1u;
+            prev = mk;
+        }
     }
 }
 
@@ -436,20 +524,33 @@ namespace {
 
 template <bool WORDS, uint32_t CS>
 void me_launch_long(hipStream_t s, const uint8_t* in, const uint8_t* ws, uint64_t n, const MeTable& t,
-                    unsigned long long* total, uint64_t* slot, uint64_t nchunks) {
-    hipLaunchKernelGGL((k_me_long<WORDS, CS>), dim3((uint32_t)gbpe_div_up(nchunks, ME_TPB)), dim3(ME_TPB), 0, s, in, ws, n,
-                       t, total, slot, nchunks);
-}
-
-// k_me_walk, or with the documents of a batch call (always the word form) k_me_walk_docs
-template <bool WORDS, uint32_t CS>
-void me_launch_walk(hipStream_t s, const uint8_t* in, const uint8_t* ws, uint64_t n, const MeTable& t, uint32_t* scratch,
-                    uint32_t* counts, uint64_t* base, uint64_t nchunks, const MeArena& ar, const MeDocs* docs) {
+                    unsigned long long* total, uint64_t* slot, uint64_t nchunks, bool special) {
     const dim3 grid((uint32_t)gbpe_div_up(nchunks, ME_TPB));
     if constexpr (WORDS) {
+        if (special) {   // (the same cuts as the special walk)
+            hipLaunchKernelGGL((k_me_long<true, CS, true>), grid, dim3(ME_TPB), 0, s, in, ws, n, t, total, slot, nchunks);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_me_long<WORDS, CS>), grid, dim3(ME_TPB), 0, s, in, ws, n, t, total, slot, nchunks);
+}
+
+// k_me_walk; with the documents of a batch call (always the word form) k_me_walk_docs; with special
+// tokens its SP form, for one buffer too (no document bit is set then: `docs` is not read)
+template <bool WORDS, uint32_t CS>
+void me_launch_walk(hipStream_t s, const uint8_t* in, const uint8_t* ws, uint64_t n, const MeTable& t, uint32_t* scratch,
+                    uint32_t* counts, uint64_t* base, uint64_t nchunks, const MeArena& ar, const MeDocs* docs,
+                    const MeSp* sp) {
+    const dim3 grid((uint32_t)gbpe_div_up(nchunks, ME_TPB));
+    if constexpr (WORDS) {
+        if (sp) {
+            hipLaunchKernelGGL((k_me_walk_docs<CS, true>), grid, dim3(ME_TPB), 0, s, in, ws, n, t, scratch, counts, base,
+                               nchunks, ar, docs ? *docs : MeDocs{}, *sp);
+            return;
+        }
         if (docs) {
             hipLaunchKernelGGL((k_me_walk_docs<CS>), grid, dim3(ME_TPB), 0, s, in, ws, n, t, scratch, counts, base, nchunks,
-                               ar, *docs);
+                               ar, *docs, MeSp{});
             return;
         }
     }
@@ -476,25 +577,31 @@ struct MeWork {   // the device arrays of one call, each 16-byte aligned inside 
     uint64_t* total;
     uint64_t* slot;       // nchunks * me_lslot(cs): arena offsets of the long segments
     unsigned long long* back;   // 16 bytes read back after k_me_long: the long-segment total, the offsets' verdict
-    // a batch call (n_docs > 0) only
+    // a batch call (n_docs > 0) or one with special tokens only
     uint32_t* doc_written;   // n_docs
     uint8_t* mask;           // n
-    uint8_t* flags;          // n, when asked for (GPT-4 rules: the document starts)
+    uint8_t* flags;          // n, when asked for: the document starts (GPT-4 rules: and the specials' edges)
+    // special tokens only
+    uint8_t* mark;           // n: gbpe_specials_mark's array
+    uint8_t* cand;           // n
 };
 
 hipError_t me_layout(gbpe_ctx* ctx, GbpeArray<uint8_t>& blk, uint64_t n, uint32_t cs, uint64_t nchunks, uint64_t nblk,
-                     uint64_t n_docs, bool flags, MeWork* w) {
+                     uint64_t n_docs, bool flags, bool special, MeWork* w) {
     const uint64_t o_counts = up16(4 * n), o_base = o_counts + up16(4 * nchunks), o_local = o_base + up16(8 * nchunks);
     const uint64_t o_bsum = o_local + up16(4 * nchunks), o_slot = o_bsum + up16(8 * (nblk + 2));
     const uint64_t o_back = o_slot + up16(8 * nchunks * me_lslot(cs)), o_docw = o_back + 16;
-    const uint64_t o_mask = o_docw + up16(4 * n_docs), o_flags = o_mask + up16(n), o_end = o_flags + (flags ? up16(n) : 0);
-    const hipError_t e = blk.reserve(ctx, (n_docs ? o_end : o_back) + 16);
+    const uint64_t o_mask = o_docw + up16(4 * n_docs), o_flags = o_mask + up16(n), o_mark = o_flags + (flags ? up16(n) : 0);
+    const uint64_t o_end = o_mark + (special ? 2 * up16(n) : 0);
+    const hipError_t e = blk.reserve(ctx, (n_docs || special ? o_end : o_back) + 16);
     if (e != hipSuccess) return e;
     uint8_t* p = blk.p;
     *w = MeWork{(uint32_t*)p, (uint32_t*)(p + o_counts), (uint64_t*)(p + o_base), (uint32_t*)(p + o_local),
                 (uint64_t*)(p + o_bsum), (uint64_t*)(p + o_bsum) + nblk + 1, (uint64_t*)(p + o_slot),
-                (unsigned long long*)(p + o_back), nullptr, nullptr, nullptr};
-    if (n_docs) w->doc_written = (uint32_t*)(p + o_docw), w->mask = p + o_mask, w->flags = p + o_flags;
+                (unsigned long long*)(p + o_back), nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (n_docs || special) w->doc_written = (uint32_t*)(p + o_docw), w->mask = p + o_mask;
+    if (flags) w->flags = p + o_flags;
+    if (special) w->mark = p + o_mark, w->cand = p + o_mark + up16(n);
     return hipSuccess;
 }
 
@@ -518,41 +625,50 @@ struct MeDocJob {   // the documents of a batch call, n_docs > 0
     uint64_t* d_tok_off;         // [0, n_docs]
 };
 
-// w.mask of a batch call: bit 0 = `the mode's per-document mask | document starts` (mode NONE:
-// document starts only), ME_DOC_BIT = a document starts here.  The first kernel checks the offsets
-// into the second word of w.back (zeroed by the caller).
-int me_docs_mask(gbpe_ctx* ctx, const uint8_t* d_in, uint64_t n, const uint8_t* d_ws, uint32_t mode, const MeDocJob& docs,
-                 const MeWork& w) {
+// w.mask of a batch call and of one with special tokens (`docs`, `sp`: at least one).  Bit 0 =
+// the mode's mask of every document — of every piece between accepted specials — alone (mode NONE:
+// nothing) | the starts of the documents, of the specials and of the pieces after them;
+// ME_DOC_BIT = a document starts here; ME_SP_BIT / ME_SPIN_BIT = a special's first / other bytes.
+// The GPT-4 rules see a piece alone through the document form of the pre-tokeniser: w.flags holds
+// the document starts, then (k_sp_accept) the pieces' too.  The other modes' masks look one byte
+// back at most, so forcing a piece's first byte is all they need.  The first kernel checks the
+// offsets into the second word of w.back (zeroed by the caller).
+int me_mask(gbpe_ctx* ctx, const uint8_t* d_in, uint64_t n, const uint8_t* d_ws, uint32_t mode, const MeDocJob* docs,
+            const gbpe_specials* sp, const MeWork& w) {
     hipStream_t s = ctx->stream;
     uint32_t* d_invalid = (uint32_t*)(w.back + 1);
     int rc = GBPE_OK;
+    if (w.flags) GBPE_HIP(ctx, hipMemsetAsync(w.flags, 0, n, s));
+    if (docs) rc = gbpe_doc_flags_launch(ctx, docs->d_doc_off, docs->n_docs, n, w.flags, w.flags ? 1u : 0u, d_invalid);
+    if (rc == GBPE_OK && sp)
+        rc = gbpe_specials_launch(ctx, sp, d_in, n, docs ? w.flags : nullptr, w.cand, w.mark,
+                                  mode == GBPE_WORDS_GPT4 ? w.flags : nullptr);
+    if (rc != GBPE_OK) return rc;
     if (mode == GBPE_WORDS_GPT4) {
-        GBPE_HIP(ctx, hipMemsetAsync(w.flags, 0, n, s));
-        rc = gbpe_doc_flags_launch(ctx, docs.d_doc_off, docs.n_docs, n, w.flags, 1u, d_invalid);
-        if (rc == GBPE_OK) rc = gbpe_pretok_gpt4_docs_launch(ctx, d_in, n, w.flags, w.mask);
+        rc = gbpe_pretok_gpt4_docs_launch(ctx, d_in, n, w.flags, w.mask);
+    } else if (mode == GBPE_WORDS_NONE) {
+        GBPE_HIP(ctx, hipMemsetAsync(w.mask, 0, n, s));
+    } else if (mode == GBPE_WORDS_MASK) {
+        hipLaunchKernelGGL(k_me_mask01, dim3((uint32_t)gbpe_div_up(n, 1024)), dim3(256), 0, s, d_ws, n, w.mask);
     } else {
-        rc = gbpe_doc_flags_launch(ctx, docs.d_doc_off, docs.n_docs, n, nullptr, 0u, d_invalid);
-        if (rc == GBPE_OK && mode == GBPE_WORDS_NONE) {
-            GBPE_HIP(ctx, hipMemsetAsync(w.mask, 0, n, s));
-        } else if (rc == GBPE_OK && mode == GBPE_WORDS_MASK) {
-            hipLaunchKernelGGL(k_me_mask01, dim3((uint32_t)gbpe_div_up(n, 1024)), dim3(256), 0, s, d_ws, n, w.mask);
-        } else if (rc == GBPE_OK) {
-            rc = gbpe_word_boundary_launch(ctx, d_in, n, w.mask);
-        }
+        rc = gbpe_word_boundary_launch(ctx, d_in, n, w.mask);
     }
-    if (rc == GBPE_OK) rc = gbpe_doc_flags_launch(ctx, docs.d_doc_off, docs.n_docs, n, w.mask, ME_DOC_BIT, nullptr);
+    if (rc == GBPE_OK && sp)
+        hipLaunchKernelGGL(k_me_sp_mask, dim3((uint32_t)gbpe_div_up(n, 4096)), dim3(256), 0, s, (const uint8_t*)w.mark, n,
+                           w.mask);
+    if (rc == GBPE_OK && docs) rc = gbpe_doc_flags_launch(ctx, docs->d_doc_off, docs->n_docs, n, w.mask, ME_DOC_BIT, nullptr);
     return rc;
 }
 
 // d_in[0, n) (and, mode MASK, d_ws[0, n)) → d_out[0, min(total, out_cap)); n > 0, the mode checked.
 // With `docs`, also d_doc_off[0, n_docs] → d_tok_off[0, n_docs]: the tokens are the word kernels'
-// under me_docs_mask's mask.  The offsets' verdict comes back with the long-segment total, the
+// under me_mask's mask; with `sp` (special tokens), of the pieces between the accepted specials.  The offsets' verdict comes back with the long-segment total, the
 // call's first synchronise, before anything is written to d_out or d_tok_off.  `what` names the
 // entry point in error texts.
-int me_run(gbpe_ctx* ctx, gbpe_bpe* bp, const char* what, const uint8_t* d_in, uint64_t n, const uint8_t* d_ws,
-           uint32_t mode, uint32_t* d_out, uint64_t out_cap, const MeDocJob* docs, uint64_t* n_out) {
+int me_run(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, const char* what, const uint8_t* d_in, uint64_t n,
+           const uint8_t* d_ws, uint32_t mode, uint32_t* d_out, uint64_t out_cap, const MeDocJob* docs, uint64_t* n_out) {
     hipStream_t s = ctx->stream;
-    const bool words = docs || mode != GBPE_WORDS_NONE;   // (a document start is a cut)
+    const bool words = docs || sp || mode != GBPE_WORDS_NONE;   // (a document start, a special's edge is a cut)
     uint32_t cs = ME_CS;
     if (words) {
         cs = (uint32_t)gbpe_debug_knob("me_cs", ME_CS_WORDS);   // (read per call: the bench and the tests run all three)
@@ -563,15 +679,17 @@ int me_run(gbpe_ctx* ctx, gbpe_bpe* bp, const char* what, const uint8_t* d_in, u
     const uint64_t nblk = gbpe_div_up(nchunks, SCAN_BLK);
     GbpeArray<uint8_t> work, mask, arena;
     MeWork w;
-    GBPE_HIP(ctx, me_layout(ctx, work, n, cs, nchunks, nblk, docs ? docs->n_docs : 0, docs && mode == GBPE_WORDS_GPT4, &w));
+    // (flags: the GPT-4 rules' piece starts; the document starts the matcher must not cross)
+    GBPE_HIP(ctx, me_layout(ctx, work, n, cs, nchunks, nblk, docs ? docs->n_docs : 0,
+                            (docs || sp) && (mode == GBPE_WORDS_GPT4 || (docs && sp)), sp != nullptr, &w));
     const MeTable t{bp->slots, bp->mask, bp->cross};
     const uint64_t cell = docs ? 16 : 8;   // of w.back: a batch call also reads the offsets' verdict
 
     GBPE_HIP(ctx, hipEventRecord(ctx->ev[0], s));
     int rc = GBPE_OK;
-    if (docs) {
+    if (docs || sp) {
         GBPE_HIP(ctx, hipMemsetAsync(w.back, 0, cell, s));
-        rc = me_docs_mask(ctx, d_in, n, d_ws, mode, *docs, w);
+        rc = me_mask(ctx, d_in, n, d_ws, mode, docs, sp, w);
         d_ws = w.mask;
     } else if (mode == GBPE_WORDS_HEURISTIC || mode == GBPE_WORDS_GPT4) {
         GBPE_HIP(ctx, mask.reserve(ctx, n));
@@ -585,9 +703,9 @@ int me_run(gbpe_ctx* ctx, gbpe_bpe* bp, const char* what, const uint8_t* d_in, u
     }
     GBPE_HIP(ctx, hipEventRecord(ctx->ev[1], s));
     // long segments: their total length sizes the heap arena (none: no arena)
-    hipError_t e = docs ? hipSuccess : hipMemsetAsync(w.back, 0, cell, s);
+    hipError_t e = docs || sp ? hipSuccess : hipMemsetAsync(w.back, 0, cell, s);
     if (e == hipSuccess) {
-        ME_DISPATCH(me_launch_long, words, cs, s, d_in, d_ws, n, t, w.back, w.slot, nchunks);
+        ME_DISPATCH(me_launch_long, words, cs, s, d_in, d_ws, n, t, w.back, w.slot, nchunks, sp != nullptr);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipEventRecord(ctx->ev[2], s);
@@ -602,8 +720,9 @@ int me_run(gbpe_ctx* ctx, gbpe_bpe* bp, const char* what, const uint8_t* d_in, u
     if (e == hipSuccess) e = hipEventRecord(ctx->ev[3], s);
     if (e == hipSuccess) {
         const MeDocs md{docs ? docs->d_doc_off : nullptr, docs ? docs->n_docs : 0, w.doc_written};
+        const MeSp ms{w.mark, sp ? gbpe_specials_ids(sp) : nullptr};
         ME_DISPATCH(me_launch_walk, words, cs, s, d_in, d_ws, n, t, w.scratch, w.counts, w.base, nchunks, ar,
-                    docs ? &md : nullptr);
+                    docs ? &md : nullptr, sp ? &ms : nullptr);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipEventRecord(ctx->ev[4], s);
@@ -655,9 +774,15 @@ int me_words_check(gbpe_ctx* ctx, const void* word_starts, uint32_t mode) {
 
 }  // namespace
 
-extern "C" int gbpe_bpe_encode_words_device(gbpe_ctx* ctx, gbpe_bpe* bp, const void* d_bytes, uint64_t n,
-                                            const void* d_word_starts, uint32_t words_mode, void* d_out, uint64_t out_cap,
-                                            uint64_t* n_out) {
+// The four entry points, each with and without a special table (`special`: sp must be one)
+namespace {
+
+int me_words_device(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, bool special, const void* d_bytes, uint64_t n,
+                    const void* d_word_starts, uint32_t words_mode, void* d_out, uint64_t out_cap, uint64_t* n_out) {
+    if (special && !sp) {
+        if (n_out) *n_out = 0;
+        return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe encode (special): no special table");
+    }
     if (!ctx || !bp || !n_out || (n && !d_bytes) || (out_cap && !d_out))
         return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
     *n_out = 0;
@@ -665,13 +790,16 @@ extern "C" int gbpe_bpe_encode_words_device(gbpe_ctx* ctx, gbpe_bpe* bp, const v
     if (rc != GBPE_OK) return rc;
     if ((uintptr_t)d_out & 3u) return gbpe_set_error(ctx, GBPE_E_INVALID, "d_out must be 4-byte aligned");
     if (n == 0) return GBPE_OK;
-    return me_run(ctx, bp, "bpe encode (words)", (const uint8_t*)d_bytes, n, (const uint8_t*)d_word_starts, words_mode,
+    return me_run(ctx, bp, sp, "bpe encode (words)", (const uint8_t*)d_bytes, n, (const uint8_t*)d_word_starts, words_mode,
                   (uint32_t*)d_out, out_cap, nullptr, n_out);
 }
 
-extern "C" int gbpe_bpe_encode_words(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* bytes, uint64_t n,
-                                     const uint8_t* word_starts, uint32_t words_mode, uint32_t* out, uint64_t out_cap,
-                                     uint64_t* n_out) {
+int me_words_host(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, bool special, const uint8_t* bytes, uint64_t n,
+                  const uint8_t* word_starts, uint32_t words_mode, uint32_t* out, uint64_t out_cap, uint64_t* n_out) {
+    if (special && !sp) {
+        if (n_out) *n_out = 0;
+        return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe encode (special): no special table");
+    }
     if (!ctx || !bp || !n_out || (n && !bytes) || (out_cap && !out))
         return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
     *n_out = 0;
@@ -688,7 +816,8 @@ extern "C" int gbpe_bpe_encode_words(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t*
     hipError_t e = hipMemcpyAsync(io.p, bytes, n, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && word_starts) e = hipMemcpyAsync(d_ws, word_starts, n, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
-        rc = me_run(ctx, bp, "bpe encode (words)", io.p, n, d_ws, words_mode, (uint32_t*)(io.p + o_out), cap, nullptr, n_out);
+        rc = me_run(ctx, bp, sp, "bpe encode (words)", io.p, n, d_ws, words_mode, (uint32_t*)(io.p + o_out), cap, nullptr,
+                    n_out);
         if (rc != GBPE_OK && rc != GBPE_E_CAPACITY) return rc;   // (synchronised there)
         const uint64_t fit = *n_out < cap ? *n_out : cap;
         if (fit) e = hipMemcpyAsync(out, io.p + o_out, fit * 4, hipMemcpyDeviceToHost, s);
@@ -699,6 +828,32 @@ extern "C" int gbpe_bpe_encode_words(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t*
     return rc;
 }
 
+}  // namespace
+
+extern "C" int gbpe_bpe_encode_words_device(gbpe_ctx* ctx, gbpe_bpe* bp, const void* d_bytes, uint64_t n,
+                                            const void* d_word_starts, uint32_t words_mode, void* d_out, uint64_t out_cap,
+                                            uint64_t* n_out) {
+    return me_words_device(ctx, bp, nullptr, false, d_bytes, n, d_word_starts, words_mode, d_out, out_cap, n_out);
+}
+
+extern "C" int gbpe_bpe_encode_special_device(gbpe_ctx* ctx, gbpe_bpe* bp, gbpe_specials* sp, const void* d_bytes, uint64_t n,
+                                              const void* d_word_starts, uint32_t words_mode, void* d_out, uint64_t out_cap,
+                                              uint64_t* n_out) {
+    return me_words_device(ctx, bp, sp, true, d_bytes, n, d_word_starts, words_mode, d_out, out_cap, n_out);
+}
+
+extern "C" int gbpe_bpe_encode_words(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* bytes, uint64_t n,
+                                     const uint8_t* word_starts, uint32_t words_mode, uint32_t* out, uint64_t out_cap,
+                                     uint64_t* n_out) {
+    return me_words_host(ctx, bp, nullptr, false, bytes, n, word_starts, words_mode, out, out_cap, n_out);
+}
+
+extern "C" int gbpe_bpe_encode_special(gbpe_ctx* ctx, gbpe_bpe* bp, gbpe_specials* sp, const uint8_t* bytes, uint64_t n,
+                                       const uint8_t* word_starts, uint32_t words_mode, uint32_t* out, uint64_t out_cap,
+                                       uint64_t* n_out) {
+    return me_words_host(ctx, bp, sp, true, bytes, n, word_starts, words_mode, out, out_cap, n_out);
+}
+
 // the whole string: no word cuts (the words contract, gpubpe.h)
 extern "C" int gbpe_bpe_encode(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* bytes, uint64_t n, uint32_t* out,
                                uint64_t out_cap, uint64_t* n_out) {
@@ -707,10 +862,15 @@ extern "C" int gbpe_bpe_encode(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* bytes
 
 // ── many documents in one call (gbpe_bpe_encode_words_batch*) ──
 
-extern "C" int gbpe_bpe_encode_words_batch_device(gbpe_ctx* ctx, gbpe_bpe* bp, const void* d_bytes, uint64_t n,
-                                                  const void* d_doc_off, uint64_t n_docs, const void* d_word_starts,
-                                                  uint32_t words_mode, void* d_out, uint64_t out_cap, void* d_tok_off,
-                                                  uint64_t* n_out) {
+namespace {
+
+int me_batch_device(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, bool special, const void* d_bytes, uint64_t n,
+                    const void* d_doc_off, uint64_t n_docs, const void* d_word_starts, uint32_t words_mode, void* d_out,
+                    uint64_t out_cap, void* d_tok_off, uint64_t* n_out) {
+    if (special && !sp) {
+        if (n_out) *n_out = 0;
+        return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe encode (special): no special table");
+    }
     if (!ctx || !bp || !n_out || !d_tok_off || (n_docs && !d_doc_off) || (n && n_docs && !d_bytes) || (out_cap && !d_out))
         return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
     *n_out = 0;
@@ -725,14 +885,17 @@ extern "C" int gbpe_bpe_encode_words_batch_device(gbpe_ctx* ctx, gbpe_bpe* bp, c
         return GBPE_OK;
     }
     const MeDocJob docs{(const uint64_t*)d_doc_off, n_docs, (uint64_t*)d_tok_off};
-    return me_run(ctx, bp, "bpe encode batch", (const uint8_t*)d_bytes, n, (const uint8_t*)d_word_starts, words_mode,
+    return me_run(ctx, bp, sp, "bpe encode batch", (const uint8_t*)d_bytes, n, (const uint8_t*)d_word_starts, words_mode,
                   (uint32_t*)d_out, out_cap, &docs, n_out);
 }
 
-extern "C" int gbpe_bpe_encode_words_batch(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* bytes, uint64_t n,
-                                           const uint64_t* doc_off, uint64_t n_docs, const uint8_t* word_starts,
-                                           uint32_t words_mode, uint32_t* out, uint64_t out_cap, uint64_t* tok_off,
-                                           uint64_t* n_out) {
+int me_batch_host(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, bool special, const uint8_t* bytes, uint64_t n,
+                  const uint64_t* doc_off, uint64_t n_docs, const uint8_t* word_starts, uint32_t words_mode, uint32_t* out,
+                  uint64_t out_cap, uint64_t* tok_off, uint64_t* n_out) {
+    if (special && !sp) {
+        if (n_out) *n_out = 0;
+        return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe encode (special): no special table");
+    }
     if (!ctx || !bp || !n_out || !tok_off || (n_docs && !doc_off) || (n && n_docs && !bytes) || (out_cap && !out))
         return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
     *n_out = 0;
@@ -757,8 +920,8 @@ extern "C" int gbpe_bpe_encode_words_batch(gbpe_ctx* ctx, gbpe_bpe* bp, const ui
     if (e == hipSuccess && word_starts) e = hipMemcpyAsync(d_ws, word_starts, n, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
         const MeDocJob docs{(const uint64_t*)io.p, n_docs, (uint64_t*)(io.p + o_tok)};
-        rc = me_run(ctx, bp, "bpe encode batch", io.p + o_in, n, d_ws, words_mode, (uint32_t*)(io.p + o_out), cap, &docs,
-                    n_out);
+        rc = me_run(ctx, bp, sp, "bpe encode batch", io.p + o_in, n, d_ws, words_mode, (uint32_t*)(io.p + o_out), cap,
+                    &docs, n_out);
         if (rc != GBPE_OK && rc != GBPE_E_CAPACITY) return rc;   // (synchronised there)
         e = hipMemcpyAsync(tok_off, io.p + o_tok, 8 * (n_docs + 1), hipMemcpyDeviceToHost, s);
         const uint64_t fit = *n_out < cap ? *n_out : cap;
@@ -768,6 +931,39 @@ extern "C" int gbpe_bpe_encode_words_batch(gbpe_ctx* ctx, gbpe_bpe* bp, const ui
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return gbpe_set_error(ctx, GBPE_E_DEVICE, "bpe encode batch failed: %s", hipGetErrorString(e));
     return rc;
+}
+
+}  // namespace
+
+extern "C" int gbpe_bpe_encode_words_batch_device(gbpe_ctx* ctx, gbpe_bpe* bp, const void* d_bytes, uint64_t n,
+                                                  const void* d_doc_off, uint64_t n_docs, const void* d_word_starts,
+                                                  uint32_t words_mode, void* d_out, uint64_t out_cap, void* d_tok_off,
+                                                  uint64_t* n_out) {
+    return me_batch_device(ctx, bp, nullptr, false, d_bytes, n, d_doc_off, n_docs, d_word_starts, words_mode, d_out, out_cap,
+                           d_tok_off, n_out);
+}
+
+extern "C" int gbpe_bpe_encode_special_batch_device(gbpe_ctx* ctx, gbpe_bpe* bp, gbpe_specials* sp, const void* d_bytes,
+                                                    uint64_t n, const void* d_doc_off, uint64_t n_docs,
+                                                    const void* d_word_starts, uint32_t words_mode, void* d_out,
+                                                    uint64_t out_cap, void* d_tok_off, uint64_t* n_out) {
+    return me_batch_device(ctx, bp, sp, true, d_bytes, n, d_doc_off, n_docs, d_word_starts, words_mode, d_out, out_cap,
+                           d_tok_off, n_out);
+}
+
+extern "C" int gbpe_bpe_encode_words_batch(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* bytes, uint64_t n,
+                                           const uint64_t* doc_off, uint64_t n_docs, const uint8_t* word_starts,
+                                           uint32_t words_mode, uint32_t* out, uint64_t out_cap, uint64_t* tok_off,
+                                           uint64_t* n_out) {
+    return me_batch_host(ctx, bp, nullptr, false, bytes, n, doc_off, n_docs, word_starts, words_mode, out, out_cap, tok_off,
+                         n_out);
+}
+
+extern "C" int gbpe_bpe_encode_special_batch(gbpe_ctx* ctx, gbpe_bpe* bp, gbpe_specials* sp, const uint8_t* bytes, uint64_t n,
+                                             const uint64_t* doc_off, uint64_t n_docs, const uint8_t* word_starts,
+                                             uint32_t words_mode, uint32_t* out, uint64_t out_cap, uint64_t* tok_off,
+                                             uint64_t* n_out) {
+    return me_batch_host(ctx, bp, sp, true, bytes, n, doc_off, n_docs, word_starts, words_mode, out, out_cap, tok_off, n_out);
 }
 
 extern "C" int gbpe_bpe_encode_last_timing(gbpe_ctx* ctx, double* ms_starts, double* ms_walk, double* ms_compact) {

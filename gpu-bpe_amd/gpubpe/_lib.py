@@ -28,6 +28,7 @@ GBPE_TRAIN_TIMING = 1 << 1
 GBPE_TRAIN_GPT4_BOUNDARIES = 1 << 2
 
 GBPE_WORDS_NONE, GBPE_WORDS_MASK, GBPE_WORDS_HEURISTIC, GBPE_WORDS_GPT4 = 0, 1, 2, 3
+GBPE_SPECIALS_MAX, GBPE_SPECIAL_MAX_BYTES = 254, 128
 
 u8p = C.POINTER(C.c_uint8)
 u32p = C.POINTER(C.c_uint32)
@@ -120,6 +121,20 @@ _SIGS = [
                                                      C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, u64p]),
     ("gbpe_bpe_encode_last_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                               C.POINTER(C.c_double)]),
+    ("gbpe_specials_upload", C.c_int, [C.c_void_p, C.c_void_p, u64p, u32p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("gbpe_specials_free", None, [C.c_void_p]),
+    ("gbpe_specials_mark", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_uint64, C.c_void_p]),
+    ("gbpe_specials_mark_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                            C.c_void_p]),
+    ("gbpe_bpe_encode_special", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                          C.c_uint32, u32p, C.c_uint64, u64p]),
+    ("gbpe_bpe_encode_special_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                 C.c_uint32, C.c_void_p, C.c_uint64, u64p]),
+    ("gbpe_bpe_encode_special_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p,
+                                                C.c_uint64, C.c_void_p, C.c_uint32, u32p, C.c_uint64, u64p, u64p]),
+    ("gbpe_bpe_encode_special_batch_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                       C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                       C.c_uint64, C.c_void_p, u64p]),
     ("gbpe_encode_last_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                           C.POINTER(C.c_double)]),
     ("gbpe_vocab_upload", C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_uint32, C.POINTER(C.c_void_p)]),

@@ -18,6 +18,8 @@
 //   encode(ctx, trie, bytes, chunkSize) -> Promise<Uint32Array>
 //   encodeBatch(ctx, trie, bytes, offsets: Float64Array, chunkSize) -> Promise<{tokens: Uint32Array, offsets: Float64Array}>
 //   bpeEncodeWordsBatch(ctx, bpe, bytes, offsets: Float64Array, wordStarts | null, mode) -> {tokens: Uint32Array, offsets: Float64Array}
+//   specialsUpload(ctx, bytes, offsets: Float64Array, ids: Uint32Array) -> external; specialsMark(ctx, specials, bytes, offsets | null) -> Uint8Array
+//   bpeEncodeSpecial(ctx, bpe, specials, bytes, wordStarts | null, mode) / bpeEncodeSpecialBatch(ctx, bpe, specials, bytes, offsets, wordStarts | null, mode)
 //   pretokenizeGpt4Batch(ctx, bytes, offsets: Float64Array) -> Uint8Array
 //   vocabUpload(ctx, bytes: Uint8Array, offsets: Float64Array) -> vocab   vocabFree(vocab)
 //   decode(ctx, vocab, tokens: Uint32Array) -> Promise<Uint8Array>
@@ -512,6 +514,21 @@ void bpe_finalize(napi_env, void* data, void*) {
     delete b;
 }
 
+struct Specials {
+    gbpe_specials* sp = nullptr;
+    Ctx* owner = nullptr;
+};
+
+void specials_finalize(napi_env, void* data, void*) {
+    Specials* s = static_cast<Specials*>(data);
+    if (s->sp) {
+        std::lock_guard<std::mutex> g(s->owner->mu);
+        gbpe_specials_free(s->sp);
+    }
+    ctx_release(s->owner);
+    delete s;
+}
+
 napi_value BpeUpload(napi_env env, napi_callback_info info) {
     size_t argc = 2;
     napi_value argv[2];
@@ -564,27 +581,33 @@ napi_value BpeEncode(napi_env env, napi_callback_info info) {
 // bpeEncodeWords(ctx, bpe, bytes, wordStarts | null, mode): the merges inside each
 // word alone (gbpe_bpe_encode_words; mode = GBPE_WORDS_*: 1 takes the mask, 2 and 3
 // compute it on the device)
-napi_value BpeEncodeWords(napi_env env, napi_callback_info info) {
-    size_t argc = 5;
-    napi_value argv[5];
+// (`special`: bpeEncodeSpecial, the same with a special table after bpe — gbpe_bpe_encode_special)
+napi_value bpe_encode_words(napi_env env, napi_callback_info info, bool special) {
+    const size_t o = special ? 1 : 0;
+    size_t argc = 6;
+    napi_value argv[6];
     NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
     Ctx* c = argc >= 1 ? unwrap_external<Ctx>(env, argv[0]) : nullptr;
     Bpe* b = argc >= 2 ? unwrap_external<Bpe>(env, argv[1]) : nullptr;
+    Specials* sp = special && argc >= 3 ? unwrap_external<Specials>(env, argv[2]) : nullptr;
     const uint8_t *data = nullptr, *ws = nullptr;
     size_t len = 0, ws_len = 0;
     uint32_t mode = 0;
-    bool ok = ctx_usable(c) && b && b->bpe && argc >= 5 && get_bytes(env, argv[2], &data, &len) &&
-              napi_get_value_uint32(env, argv[4], &mode) == napi_ok;
+    bool ok = ctx_usable(c) && b && b->bpe && (!special || (sp && sp->sp)) && argc >= 5 + o &&
+              get_bytes(env, argv[2 + o], &data, &len) && napi_get_value_uint32(env, argv[4 + o], &mode) == napi_ok;
     bool has_ws = false;
     if (ok) {
         napi_valuetype vt;
-        ok = napi_typeof(env, argv[3], &vt) == napi_ok;
+        ok = napi_typeof(env, argv[3 + o], &vt) == napi_ok;
         has_ws = ok && vt != napi_null && vt != napi_undefined;
-        if (has_ws) ok = get_bytes(env, argv[3], &ws, &ws_len) && ws_len == len;
+        if (has_ws) ok = get_bytes(env, argv[3 + o], &ws, &ws_len) && ws_len == len;
     }
     if (!ok) {
         napi_throw_type_error(env, nullptr,
-                              "bpeEncodeWords(ctx, bpe, Uint8Array, wordStarts: Uint8Array of the same length | null, mode)");
+                              special ? "bpeEncodeSpecial(ctx, bpe, specials, Uint8Array, wordStarts: Uint8Array of the same "
+                                        "length | null, mode)"
+                                      : "bpeEncodeWords(ctx, bpe, Uint8Array, wordStarts: Uint8Array of the same length | "
+                                        "null, mode)");
         return nullptr;
     }
     static const uint8_t kNoByte = 0;
@@ -592,11 +615,15 @@ napi_value BpeEncodeWords(napi_env env, napi_callback_info info) {
     std::vector<uint32_t> out(len ? len : 1);
     uint64_t n = 0;
     std::unique_lock<std::mutex> g(c->mu);
-    int rc = gbpe_bpe_encode_words(c->ctx, b->bpe, data, len, has_ws ? ws : nullptr, mode, out.data(), out.size(), &n);
+    const uint8_t* m = has_ws ? ws : nullptr;
+    int rc = special ? gbpe_bpe_encode_special(c->ctx, b->bpe, sp->sp, data, len, m, mode, out.data(), out.size(), &n)
+                     : gbpe_bpe_encode_words(c->ctx, b->bpe, data, len, m, mode, out.data(), out.size(), &n);
     g.unlock();
-    if (rc != GBPE_OK) return throw_status(env, c->ctx, "bpe encode (words)", rc);
+    if (rc != GBPE_OK) return throw_status(env, c->ctx, special ? "bpe encode (special)" : "bpe encode (words)", rc);
     return make_u32_array(env, out.data(), (size_t)n);
 }
+napi_value BpeEncodeWords(napi_env env, napi_callback_info info) { return bpe_encode_words(env, info, false); }
+napi_value BpeEncodeSpecial(napi_env env, napi_callback_info info) { return bpe_encode_words(env, info, true); }
 
 // document offsets as a Float64Array of non-negative integers (exact below 2^53), D + 1 >= 1 entries
 bool get_doc_offsets(napi_env env, napi_value v, std::vector<uint64_t>* out) {
@@ -628,29 +655,35 @@ napi_value make_f64_array(napi_env env, const std::vector<uint64_t>& v) {
 
 // bpeEncodeWordsBatch(ctx, bpe, bytes, offsets, wordStarts | null, mode) -> { tokens, offsets }: many
 // documents in one call (gbpe_bpe_encode_words_batch), each encoded as bpeEncodeWords encodes it alone
-napi_value BpeEncodeWordsBatch(napi_env env, napi_callback_info info) {
-    size_t argc = 6;
-    napi_value argv[6];
+// (`special`: bpeEncodeSpecialBatch, the same with a special table after bpe — gbpe_bpe_encode_special_batch)
+napi_value bpe_encode_words_batch(napi_env env, napi_callback_info info, bool special) {
+    const size_t o = special ? 1 : 0;
+    size_t argc = 7;
+    napi_value argv[7];
     NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
     Ctx* c = argc >= 1 ? unwrap_external<Ctx>(env, argv[0]) : nullptr;
     Bpe* b = argc >= 2 ? unwrap_external<Bpe>(env, argv[1]) : nullptr;
+    Specials* sp = special && argc >= 3 ? unwrap_external<Specials>(env, argv[2]) : nullptr;
     const uint8_t *data = nullptr, *ws = nullptr;
     size_t len = 0, ws_len = 0;
     uint32_t mode = 0;
     std::vector<uint64_t> doc_off;
-    bool ok = ctx_usable(c) && b && b->bpe && argc >= 6 && get_bytes(env, argv[2], &data, &len) &&
-              get_doc_offsets(env, argv[3], &doc_off) && napi_get_value_uint32(env, argv[5], &mode) == napi_ok;
+    bool ok = ctx_usable(c) && b && b->bpe && (!special || (sp && sp->sp)) && argc >= 6 + o &&
+              get_bytes(env, argv[2 + o], &data, &len) && get_doc_offsets(env, argv[3 + o], &doc_off) &&
+              napi_get_value_uint32(env, argv[5 + o], &mode) == napi_ok;
     bool has_ws = false;
     if (ok) {
         napi_valuetype vt;
-        ok = napi_typeof(env, argv[4], &vt) == napi_ok;
+        ok = napi_typeof(env, argv[4 + o], &vt) == napi_ok;
         has_ws = ok && vt != napi_null && vt != napi_undefined;
-        if (has_ws) ok = get_bytes(env, argv[4], &ws, &ws_len) && ws_len == len;
+        if (has_ws) ok = get_bytes(env, argv[4 + o], &ws, &ws_len) && ws_len == len;
     }
     if (!ok) {
         napi_throw_type_error(env, nullptr,
-                              "bpeEncodeWordsBatch(ctx, bpe, Uint8Array, offsets: Float64Array of non-negative integers, "
-                              "wordStarts: Uint8Array of the same length | null, mode)");
+                              special ? "bpeEncodeSpecialBatch(ctx, bpe, specials, Uint8Array, offsets: Float64Array of "
+                                        "non-negative integers, wordStarts: Uint8Array of the same length | null, mode)"
+                                      : "bpeEncodeWordsBatch(ctx, bpe, Uint8Array, offsets: Float64Array of non-negative "
+                                        "integers, wordStarts: Uint8Array of the same length | null, mode)");
         return nullptr;
     }
     static const uint8_t kNoByte = 0;
@@ -659,15 +692,95 @@ napi_value BpeEncodeWordsBatch(napi_env env, napi_callback_info info) {
     std::vector<uint64_t> tok_off(doc_off.size(), 0);
     uint64_t n = 0;
     std::unique_lock<std::mutex> g(c->mu);
-    int rc = gbpe_bpe_encode_words_batch(c->ctx, b->bpe, data, len, doc_off.data(), doc_off.size() - 1,
-                                         has_ws ? ws : nullptr, mode, out.data(), out.size(), tok_off.data(), &n);
+    const uint8_t* m = has_ws ? ws : nullptr;
+    int rc = special ? gbpe_bpe_encode_special_batch(c->ctx, b->bpe, sp->sp, data, len, doc_off.data(), doc_off.size() - 1, m,
+                                                     mode, out.data(), out.size(), tok_off.data(), &n)
+                     : gbpe_bpe_encode_words_batch(c->ctx, b->bpe, data, len, doc_off.data(), doc_off.size() - 1, m, mode,
+                                                   out.data(), out.size(), tok_off.data(), &n);
     g.unlock();
-    if (rc != GBPE_OK) return throw_status(env, c->ctx, "bpe encode batch", rc);
+    if (rc != GBPE_OK) return throw_status(env, c->ctx, special ? "bpe encode batch (special)" : "bpe encode batch", rc);
     napi_value obj;
     NAPI_CALL(env, napi_create_object(env, &obj));
     NAPI_CALL(env, napi_set_named_property(env, obj, "tokens", make_u32_array(env, out.data(), (size_t)n)));
     NAPI_CALL(env, napi_set_named_property(env, obj, "offsets", make_f64_array(env, tok_off)));
     return obj;
+}
+napi_value BpeEncodeWordsBatch(napi_env env, napi_callback_info info) { return bpe_encode_words_batch(env, info, false); }
+napi_value BpeEncodeSpecialBatch(napi_env env, napi_callback_info info) { return bpe_encode_words_batch(env, info, true); }
+
+// specialsUpload(ctx, bytes: Uint8Array, offsets: Float64Array, ids: Uint32Array) -> external: special i is
+// bytes[offsets[i], offsets[i + 1]) with id ids[i] (gbpe_specials_upload)
+napi_value SpecialsUpload(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value argv[4];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Ctx* c = argc >= 1 ? unwrap_external<Ctx>(env, argv[0]) : nullptr;
+    const uint8_t* data = nullptr;
+    const uint32_t* ids = nullptr;
+    size_t len = 0, n_ids = 0;
+    std::vector<uint64_t> offs;
+    static const uint8_t kNoByte = 0;
+    if (!ctx_usable(c) || argc < 4 || !get_bytes(env, argv[1], &data, &len) || !get_doc_offsets(env, argv[2], &offs) ||
+        !get_u32s(env, argv[3], &ids, &n_ids) || n_ids + 1 != offs.size() || offs.back() > len) {
+        napi_throw_type_error(env, nullptr, "specialsUpload(ctx, Uint8Array, offsets: Float64Array, ids: Uint32Array)");
+        return nullptr;
+    }
+    for (size_t i = 0; i + 1 < offs.size(); ++i) {
+        if (offs[i + 1] < offs[i]) {
+            napi_throw_type_error(env, nullptr, "specialsUpload: offsets decrease");
+            return nullptr;
+        }
+    }
+    auto* s = new Specials();
+    const uint32_t no_id = 0;
+    std::unique_lock<std::mutex> g(c->mu);
+    int rc = gbpe_specials_upload(c->ctx, data ? data : &kNoByte, offs.data(), ids ? ids : &no_id, (uint32_t)n_ids, &s->sp);
+    g.unlock();
+    if (rc != GBPE_OK) {
+        delete s;
+        return throw_status(env, c->ctx, "specials upload", rc);
+    }
+    s->owner = c;
+    ++c->refs;
+    napi_value ext;
+    NAPI_CALL(env, napi_create_external(env, s, specials_finalize, nullptr, &ext));
+    return ext;
+}
+
+// specialsMark(ctx, specials, bytes, offsets | null) -> Uint8Array: 0 / 1 + index / 255 per byte (gbpe_specials_mark)
+napi_value SpecialsMark(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value argv[4];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Ctx* c = argc >= 1 ? unwrap_external<Ctx>(env, argv[0]) : nullptr;
+    Specials* sp = argc >= 2 ? unwrap_external<Specials>(env, argv[1]) : nullptr;
+    const uint8_t* data = nullptr;
+    size_t len = 0;
+    std::vector<uint64_t> doc_off;
+    bool ok = ctx_usable(c) && sp && sp->sp && argc >= 3 && get_bytes(env, argv[2], &data, &len);
+    bool has_off = false;
+    if (ok && argc >= 4) {
+        napi_valuetype vt;
+        ok = napi_typeof(env, argv[3], &vt) == napi_ok;
+        has_off = ok && vt != napi_null && vt != napi_undefined;
+        if (has_off) ok = get_doc_offsets(env, argv[3], &doc_off);
+    }
+    if (!ok) {
+        napi_throw_type_error(env, nullptr,
+                              "specialsMark(ctx, specials, Uint8Array, offsets: Float64Array of non-negative integers | null)");
+        return nullptr;
+    }
+    napi_value ab, ta;
+    void* dst = nullptr;
+    NAPI_CALL(env, napi_create_arraybuffer(env, len, &dst, &ab));
+    if (len) memset(dst, 0, len);
+    std::unique_lock<std::mutex> g(c->mu);
+    int rc = gbpe_specials_mark(c->ctx, sp->sp, data, len, has_off ? doc_off.data() : nullptr,
+                                has_off ? doc_off.size() - 1 : 0, static_cast<uint8_t*>(dst));
+    g.unlock();
+    if (rc != GBPE_OK) return throw_status(env, c->ctx, "specialsMark", rc);
+    NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, len, ab, 0, &ta));
+    return ta;
 }
 
 // pretokenizeGpt4Batch(ctx, bytes, offsets) -> Uint8Array: each document's own GPT-4 word starts
@@ -1091,6 +1204,10 @@ napi_value Init(napi_env env, napi_value exports) {
         {"encode", nullptr, Encode, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"encodeBatch", nullptr, EncodeBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"bpeEncodeWordsBatch", nullptr, BpeEncodeWordsBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"specialsUpload", nullptr, SpecialsUpload, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"specialsMark", nullptr, SpecialsMark, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"bpeEncodeSpecial", nullptr, BpeEncodeSpecial, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"bpeEncodeSpecialBatch", nullptr, BpeEncodeSpecialBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"pretokenizeGpt4Batch", nullptr, PretokenizeGpt4Batch, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"vocabUpload", nullptr, VocabUpload, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"vocabFree", nullptr, VocabFree, nullptr, nullptr, nullptr, napi_default, nullptr},

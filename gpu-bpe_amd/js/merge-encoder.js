@@ -6,7 +6,12 @@
  * (model = { vocab, vocabStrings, merges }).  opts = { wordStarts: Uint8Array (one
  * entry per byte, non-zero = word start) } or { words: 'gpt4' | 'heuristic' } (the
  * mask computed on the device); without opts no word is cut.  encodeBatch(docs,
- * opts) encodes many documents in one call.  Node 12 syntax.
+ * opts) encodes many documents in one call.  new MergeEncoder(engine, model,
+ * { specialTokens: { '<|endoftext|>': id, ... } | Map of string or Uint8Array to id })
+ * matches those strings on the raw bytes: each is one token and the text between
+ * them is encoded as if alone; opts.special === false gives the result without the
+ * table, findSpecial(bytes, offsets) the matches (0 / 1 + index / 255 per byte).
+ * Node 12 syntax.
  */
 import { native } from './native.js';
 
@@ -25,31 +30,88 @@ export function flattenDocuments(docs, offsets) {
     return { bytes: bytes, offsets: offs };
 }
 
+/**
+ * A special table checked on the host: [{ bytes: Uint8Array, id }] in the given order.
+ * 1 to 254 distinct strings of 1 to 128 bytes, ids in [0, 2^32); anything else throws.
+ */
+export function checkedSpecialTokens(specialTokens) {
+    const entries = specialTokens instanceof Map ? Array.from(specialTokens.entries())
+        : (specialTokens && typeof specialTokens === 'object' ? Object.keys(specialTokens).map(function (k) {
+            return [k, specialTokens[k]];
+        }) : null);
+    if (entries === null) throw new TypeError('specialTokens: give an object or a Map of string or Uint8Array to id');
+    const seen = new Set();
+    const table = entries.map(function (e) {
+        const raw = typeof e[0] === 'string' ? new Uint8Array(Buffer.from(e[0], 'utf8')) : e[0];
+        if (!(raw instanceof Uint8Array)) throw new TypeError('specialTokens: a key must be a string or a Uint8Array');
+        if (raw.length < 1 || raw.length > 128) throw new RangeError('specialTokens: an entry has 1 to 128 bytes');
+        const key = Buffer.from(raw).toString('hex');
+        if (seen.has(key)) throw new RangeError('specialTokens: an entry is given twice');
+        seen.add(key);
+        if (!Number.isInteger(e[1]) || e[1] < 0 || e[1] > 0xFFFFFFFF) {
+            throw new RangeError('specialTokens: an id must be an integer in [0, 2^32)');
+        }
+        return { bytes: raw, id: e[1] };
+    });
+    if (table.length < 1 || table.length > 254) throw new RangeError('specialTokens: 1 to 254 entries');
+    return table;
+}
+
 export class MergeEncoder {
-    constructor(engine, model) {
+    constructor(engine, model, opts) {
         this._engine = engine;
         this._model = model;
+        this._sp = null;
+        this.specialTokens = opts && opts.specialTokens ? checkedSpecialTokens(opts.specialTokens) : null;
         const merges = model.merges || [];
         const flat = new Uint32Array(merges.length * 3);
         merges.forEach(function (m, i) { flat[3 * i] = m[0]; flat[3 * i + 1] = m[1]; flat[3 * i + 2] = m[2]; });
         this._h = native().bpeUpload(engine.device, flat);
+        if (this.specialTokens !== null) {
+            const flatSp = flattenDocuments(this.specialTokens.map(function (e) { return e.bytes; }));
+            const ids = Uint32Array.from(this.specialTokens.map(function (e) { return e.id; }));
+            this._sp = native().specialsUpload(engine.device, flatSp.bytes, flatSp.offsets, ids);
+        }
+    }
+
+    /** The table a call uses: the encoder's unless opts.special === false; opts.special === true insists on one. */
+    _special(opts) {
+        const special = opts && opts.special !== undefined && opts.special !== null ? opts.special : null;
+        if (special === false) return null;
+        if (special === true && this._sp === null) throw new TypeError('special: true on an encoder without specialTokens');
+        return this._sp;
+    }
+
+    /** The matches of the special table: Uint8Array, 0 / 1 + index / 255 per byte; offsets: the documents'. */
+    findSpecial(bytes, offsets) {
+        if (this._sp === null) throw new TypeError('findSpecial: the encoder has no specialTokens');
+        const flat = Array.isArray(bytes) || (offsets !== undefined && offsets !== null) ? flattenDocuments(bytes, offsets) : null;
+        return flat === null ? native().specialsMark(this._engine.device, this._sp, bytes, null)
+            : native().specialsMark(this._engine.device, this._sp, flat.bytes, flat.offsets);
     }
 
     encodeBytes(bytes, opts) {
         const ws = opts && opts.wordStarts !== undefined && opts.wordStarts !== null ? opts.wordStarts : null;
         const words = opts && opts.words !== undefined && opts.words !== null ? opts.words : null;
-        if (ws === null && words === null) return native().bpeEncode(this._engine.device, this._h, bytes);
+        const sp = this._special(opts);
+        const dev = this._engine.device;
+        const h = this._h;
+        const run = function (mask, mode) {
+            return sp !== null ? native().bpeEncodeSpecial(dev, h, sp, bytes, mask, mode)
+                : native().bpeEncodeWords(dev, h, bytes, mask, mode);
+        };
+        if (ws === null && words === null) return sp !== null ? run(null, 0) : native().bpeEncode(dev, h, bytes);
         if (ws !== null && words !== null) throw new TypeError('encodeBytes: give wordStarts or words, not both');
         if (ws !== null) {
             if (!(ws instanceof Uint8Array) || ws.length !== bytes.length) {
                 throw new TypeError('encodeBytes: wordStarts must be a Uint8Array with one entry per byte');
             }
-            return native().bpeEncodeWords(this._engine.device, this._h, bytes, ws, WORDS_MASK);
+            return run(ws, WORDS_MASK);
         }
         if (!Object.prototype.hasOwnProperty.call(WORDS_MODES, words)) {
             throw new TypeError("encodeBytes: words must be 'gpt4' or 'heuristic'");
         }
-        return native().bpeEncodeWords(this._engine.device, this._h, bytes, null, WORDS_MODES[words]);
+        return run(null, WORDS_MODES[words]);
     }
 
     /**
@@ -76,6 +138,10 @@ export class MergeEncoder {
                 throw new TypeError("encodeBatch: words must be 'gpt4' or 'heuristic'");
             }
             mode = WORDS_MODES[words];
+        }
+        const sp = this._special(opts);
+        if (sp !== null) {
+            return native().bpeEncodeSpecialBatch(this._engine.device, this._h, sp, flat.bytes, flat.offsets, ws, mode);
         }
         return native().bpeEncodeWordsBatch(this._engine.device, this._h, flat.bytes, flat.offsets, ws, mode);
     }

@@ -448,6 +448,66 @@ int gbpe_bpe_encode_words_batch_device(gbpe_ctx* ctx, gbpe_bpe* bpe, const void*
  * compaction (a batch call: with the document token offsets) */
 int gbpe_bpe_encode_last_timing(gbpe_ctx* ctx, double* ms_starts, double* ms_walk, double* ms_compact);
 
+/* ── special tokens of the merge-rank encode ──────────────────
+ * A special table is 1 to GBPE_SPECIALS_MAX distinct byte strings of 1 to
+ * GBPE_SPECIAL_MAX_BYTES bytes, each with an id of the caller's choosing (any
+ * u32, not checked against the model).  Matching is on the raw bytes, before any
+ * pre-tokenisation: scan left to right; where one or more specials match, take the
+ * longest and resume just past it; otherwise advance one byte.  The matches are
+ * leftmost, longest at a position, and do not overlap.  In a batch call a special
+ * lies wholly inside one document: a string that straddles a document start is not
+ * a match (a shorter special at the same position that fits still is). */
+#define GBPE_SPECIALS_MAX       254u
+#define GBPE_SPECIAL_MAX_BYTES  128u
+typedef struct gbpe_specials gbpe_specials;
+/* Special i is bytes[offsets[i] .. offsets[i+1]) with id ids[i] (gbpe_vocab_upload's
+ * layout).  GBPE_E_INVALID with nothing allocated and *out = NULL: no entry or more
+ * than GBPE_SPECIALS_MAX, an empty entry, one above GBPE_SPECIAL_MAX_BYTES bytes,
+ * the same string twice. */
+int  gbpe_specials_upload(gbpe_ctx* ctx, const uint8_t* bytes, const uint64_t* offsets, const uint32_t* ids,
+                          uint32_t n_specials, gbpe_specials** out);
+void gbpe_specials_free(gbpe_specials* specials);
+/* The matcher alone: mark_out[i] is 0 for an ordinary byte, 1 + i's index in the
+ * table at the first byte of an accepted special and 255 on its other bytes.
+ * doc_off == NULL with n_docs == 0: one document.  Otherwise doc_off has
+ * n_docs + 1 entries (gbpe_pretokenize_gpt4_batch's rules): bad offsets are
+ * GBPE_E_INVALID with mark_out untouched, n == 0 or n_docs == 0 is GBPE_OK with
+ * nothing written. */
+int gbpe_specials_mark(gbpe_ctx* ctx, gbpe_specials* specials, const uint8_t* bytes, uint64_t n,
+                       const uint64_t* doc_off, uint64_t n_docs, uint8_t* mark_out);
+/* Device-resident variant: d_bytes and d_mark_out of any alignment, d_doc_off (u64)
+ * 8-byte aligned.  Only [0, n) of each is touched. */
+int gbpe_specials_mark_device(gbpe_ctx* ctx, gbpe_specials* specials, const void* d_bytes, uint64_t n,
+                              const void* d_doc_off, uint64_t n_docs, void* d_mark_out);
+/* gbpe_bpe_encode_words* with a special table.  The accepted specials cut a document
+ * into pieces, the maximal runs of bytes outside every accepted special; the output
+ * is, in order, what gbpe_bpe_encode_words returns for each piece ALONE in the
+ * call's mode, and each special's id as one token.  GBPE_WORDS_GPT4 and
+ * GBPE_WORDS_HEURISTIC: the word starts are those of the piece alone (not the whole
+ * buffer's with the specials' edges forced: "it" EOT "'s" has word starts 1 1 in
+ * its last piece).  GBPE_WORDS_MASK: the caller's mask restricted to the piece, its
+ * first byte forced; the entries under a special's bytes are ignored.
+ * GBPE_WORDS_NONE: each piece gets gbpe_bpe_encode's tokens.  With a table that
+ * never matches the tokens are those of the call without one.  specials == NULL is
+ * GBPE_E_INVALID; everything else — arguments, alignment, GBPE_E_CAPACITY, the size
+ * query, tok_off, bad offsets — is the contract of the call of the same name
+ * without `_special`.  gbpe_bpe_encode_last_timing reports these calls: matching
+ * and the flags count under ms_starts. */
+int gbpe_bpe_encode_special(gbpe_ctx* ctx, gbpe_bpe* bpe, gbpe_specials* specials, const uint8_t* bytes, uint64_t n,
+                            const uint8_t* word_starts, uint32_t words_mode, uint32_t* out, uint64_t out_cap,
+                            uint64_t* n_out);
+int gbpe_bpe_encode_special_device(gbpe_ctx* ctx, gbpe_bpe* bpe, gbpe_specials* specials, const void* d_bytes, uint64_t n,
+                                   const void* d_word_starts, uint32_t words_mode, void* d_out, uint64_t out_cap,
+                                   uint64_t* n_out);
+int gbpe_bpe_encode_special_batch(gbpe_ctx* ctx, gbpe_bpe* bpe, gbpe_specials* specials, const uint8_t* bytes, uint64_t n,
+                                  const uint64_t* doc_off, uint64_t n_docs, const uint8_t* word_starts,
+                                  uint32_t words_mode, uint32_t* out, uint64_t out_cap, uint64_t* tok_off,
+                                  uint64_t* n_out);
+int gbpe_bpe_encode_special_batch_device(gbpe_ctx* ctx, gbpe_bpe* bpe, gbpe_specials* specials, const void* d_bytes,
+                                         uint64_t n, const void* d_doc_off, uint64_t n_docs, const void* d_word_starts,
+                                         uint32_t words_mode, void* d_out, uint64_t out_cap, void* d_tok_off,
+                                         uint64_t* n_out);
+
 /* device ms of the last encode's kernels (walk, scan, compact); after a batch call:
  * the walk, every scan and table kernel (document table, descriptors, count scan),
  * the compaction with the document token offsets (the last group's, when the host
