@@ -12,6 +12,11 @@
 // A merge whose operand is created by a LATER merge (or never) never fires in
 // the reference; such merges are dropped on upload, as are repeated pairs
 // (the first rank wins, tokenizer-manager.js:30-33).
+// Both facts need every new id to be fresh: at least 256 and given by one entry of the
+// list only.  An id that was in the stream before (a byte's, an earlier entry's) lets a
+// later rank's merge feed an earlier one's pair, and has no single first and last byte;
+// gbpe_bpe_upload rejects such a list (GBPE_E_INVALID).  On every other list the result
+// is exact, the pair (0,0) included: a slot's .w, not its pid, says that it is occupied.
 //
 // k_me_walk: one lane per chunk (4096 bytes); it owns the segments that START in
 // its chunk and BPE-encodes each in place (rank lookups in an L2-resident
@@ -66,7 +71,7 @@ struct MeArena {   // per long segment at offset `off` (bytes of all long segmen
 };
 
 struct MeTable {
-    const uint4* slots;   // {pid, rank, new id, 0}; pid 0 = empty ((0,0) never merges: token 0 never pairs)
+    const uint4* slots;   // {pid, rank, new id, occupied}; .w 0 = empty (pid 0 is the pair (0,0), a merge like any other)
     uint32_t mask;
     const uint32_t* cross;   // 65536-bit: (u << 8 | v) set iff some merge joins a token ending in u to one starting with v
 };
@@ -76,8 +81,8 @@ __device__ __forceinline__ uint4 me_find(const MeTable& t, uint32_t pid) {
     for (uint32_t p = 0; p <= t.mask; ++p) {
         const uint32_t idx = (h + ((p * (p + 1)) >> 1)) & t.mask;
         const uint4 e = t.slots[idx];
+        if (e.w == 0u) break;   // (tested first: an empty slot's pid reads 0, the pair (0,0))
         if (e.x == pid) return e;
-        if (e.x == 0u) break;
     }
     return make_uint4(0u, ME_NONE, 0u, 0u);
 }
@@ -453,10 +458,9 @@ extern "C" int gbpe_bpe_upload(gbpe_ctx* ctx, const uint32_t* merges, uint32_t n
     if (!ctx || !out || (n_merges && !merges)) return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe upload: bad arguments");
     *out = nullptr;
     // live merges: both operands exist (bytes, or created by an earlier merge), first rank of a pair
-    std::vector<int64_t> created(1u << 16, -1);
     std::vector<uint8_t> first(1u << 16, 0), last(1u << 16, 0);
-    for (uint32_t b = 0; b < 256; ++b) { created[b] = -1; first[b] = last[b] = (uint8_t)b; }
-    std::vector<uint8_t> exists(1u << 16, 0);
+    for (uint32_t b = 0; b < 256; ++b) first[b] = last[b] = (uint8_t)b;
+    std::vector<uint8_t> exists(1u << 16, 0), given(1u << 16, 0);   // given: the new id of an entry, live or not
     for (uint32_t b = 0; b < 256; ++b) exists[b] = 1;
     uint32_t slots = 16;
     while (slots < 2u * n_merges + 16) slots <<= 1;
@@ -467,9 +471,15 @@ extern "C" int gbpe_bpe_upload(gbpe_ctx* ctx, const uint32_t* merges, uint32_t n
         const uint32_t a = merges[3 * (uint64_t)r], b = merges[3 * (uint64_t)r + 1], id = merges[3 * (uint64_t)r + 2];
         if (a > 0xFFFFu || b > 0xFFFFu || id > 0xFFFFu)
             return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe upload: merge %u has an id above 0xFFFF", r);
+        // a new id must be fresh: one that was in the stream before (a byte, an earlier entry's) breaks
+        // "ranks in order = lowest-rank adjacent pair first", and its first / last byte would be two things
+        if (id < 256u)
+            return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe upload: merge %u has the new id %u, a byte's", r, id);
+        if (given[id])
+            return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe upload: merge %u gives the new id %u a second time", r, id);
+        given[id] = 1;
         if (!exists[a] || !exists[b]) continue;   // an operand that does not exist yet: never fires
         const uint32_t pid = (a << 16) | b;
-        if (pid == 0) continue;
         uint32_t h = 0;
         {   // same hash / probing as the device
             uint32_t x = pid;
@@ -479,18 +489,16 @@ extern "C" int gbpe_bpe_upload(gbpe_ctx* ctx, const uint32_t* merges, uint32_t n
         bool dup = false;
         for (uint32_t p = 0; p < slots; ++p) {
             const uint32_t idx = (h + ((p * (p + 1)) >> 1)) & (slots - 1);
+            if (tab[idx].w == 0) { tab[idx] = make_uint4(pid, r, id, 1); break; }
             if (tab[idx].x == pid) { dup = true; break; }
-            if (tab[idx].x == 0) { tab[idx] = make_uint4(pid, r, id, 0); break; }
         }
         if (dup) continue;   // the first rank of a pair wins (tokenizer-manager.js:30-33)
         ++live;
         const uint32_t k = ((uint32_t)last[a] << 8) | first[b];
         cross[k >> 5] |= 1u << (k & 31u);
-        if (!exists[id]) {
-            exists[id] = 1;
-            first[id] = first[a];
-            last[id] = last[b];
-        }
+        exists[id] = 1;   // (fresh: no earlier entry set these)
+        first[id] = first[a];
+        last[id] = last[b];
     }
     auto* bp = new (std::nothrow) gbpe_bpe();
     if (!bp) return gbpe_set_error(ctx, GBPE_E_OOM, "host allocation failed");

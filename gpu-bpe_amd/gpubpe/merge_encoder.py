@@ -4,7 +4,13 @@ string, through gbpe_bpe_upload / gbpe_bpe_encode — or, with word starts, insi
 each word alone (gbpe_bpe_encode_words: pre-tokenise, then BPE per word); many
 documents in one call through gbpe_bpe_encode_words_batch.  With special tokens
 (gbpe_bpe_encode_special*): strings such as <|endoftext|> are matched on the raw
-bytes and become one token each; the text between them is encoded as if alone."""
+bytes and become one token each; the text between them is encoded as if alone.
+
+The result is exact for every merge list whose new ids are at least 256 and distinct
+(in any order; repeated pairs, the pair (0, 0) and operands created later or never
+included).  Any other list (a new id below 256, or one an earlier entry of the list
+gave) raises GpuBpeError with GBPE_E_INVALID at construction; the message names the
+merge."""
 from __future__ import annotations
 
 import ctypes as C

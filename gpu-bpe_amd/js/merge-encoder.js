@@ -11,6 +11,10 @@
  * matches those strings on the raw bytes: each is one token and the text between
  * them is encoded as if alone; opts.special === false gives the result without the
  * table, findSpecial(bytes, offsets) the matches (0 / 1 + index / 255 per byte).
+ * Exact for every merge list whose new ids are at least 256 and distinct (any order,
+ * repeated pairs, the pair (0, 0) and operands created later or never included); a
+ * new id below 256 or given twice makes the constructor throw (GBPE_E_INVALID, the
+ * message names the merge).
  * Node 12 syntax.
  */
 import { native } from './native.js';

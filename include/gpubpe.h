@@ -374,8 +374,14 @@ int gbpe_encode_batch_device(gbpe_ctx* ctx, gbpe_trie* trie, const void* d_bytes
                              uint64_t n_docs, uint32_t chunk_size, void* d_out, uint64_t out_cap, void* d_tok_off,
                              uint64_t* n_out);
 /* ── merge-rank encode: TokenizerManager.encode (tokenizer-manager.js:13-61) ──
- * merges = [a, b, newId] x n in learned order.  Exact for any merge list: a
- * merge whose operand is only created later never fires (as in the reference).
+ * merges = [a, b, newId] x n in learned order, every id at most 0xFFFF.  Exact for
+ * every list whose new ids are fresh: each at least 256 and given by one entry only.
+ * On that domain a merge whose operand is only created later never fires, a repeated
+ * pair keeps its first rank and the pair (0, 0) merges like any other (all as in the
+ * reference); new ids may come in any order, 0xFFFF among them.  Any other list —
+ * a new id below 256, or one that an earlier entry of the list gave, whether or not
+ * that entry can fire — is GBPE_E_INVALID at upload: *out = NULL, nothing is
+ * allocated, and gbpe_last_error names the merge's index.
  * gbpe_bpe_encode is gbpe_bpe_encode_words (below) with GBPE_WORDS_NONE and no
  * mask, and has its contract: on GBPE_E_CAPACITY *n_out holds the required token
  * count and the first out_cap tokens are in place; out == NULL goes with

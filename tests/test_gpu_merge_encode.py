@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(HERE), "gpu-bpe_amd"))
 
 import bpe_oracle as O  # noqa: E402
 from gpubpe import BPEEngine, MergeEncoder, synth  # noqa: E402
+from merge_models import np_merge_order as _np_merge_order  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -60,29 +61,6 @@ def test_merge_encode_edges(engine):
     for merges, text in cases:
         enc = MergeEncoder(engine, merges)
         assert enc.encode_bytes(text).tolist() == O.encode_merge_order(text, merges), (merges, text[:20])
-
-
-def _np_merge_order(data: bytes, merges) -> np.ndarray:
-    """numpy form of the oracle's encode_merge_order (one pass per merge, every
-    occurrence left to right; runs of a == b pair up from their left end)."""
-    tok = np.frombuffer(data, np.uint8).astype(np.int64)
-    for a, b, nid in (m[:3] for m in merges):
-        if tok.size < 2:
-            break
-        idx = np.flatnonzero((tok[:-1] == a) & (tok[1:] == b))
-        if idx.size == 0:
-            continue
-        if a == b:
-            k = np.arange(idx.size)
-            start = np.ones(idx.size, bool)
-            start[1:] = idx[1:] != idx[:-1] + 1
-            rs = np.maximum.accumulate(np.where(start, k, 0))
-            idx = idx[(k - rs) % 2 == 0]
-        tok[idx] = nid
-        rm = np.zeros(tok.size, bool)
-        rm[idx + 1] = True
-        tok = tok[~rm]
-    return tok
 
 
 def test_merge_encode_long_segment(engine):
