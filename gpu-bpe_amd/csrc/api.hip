@@ -57,6 +57,8 @@ static const char* const kKernelNames[] = {
     "k_sp_accept",            // the sequential scan's matches: a chain from every uncovered candidate
     "k_me_sp_mask",           // the specials' spans and edges into the walk's mask
     "k_me_walk_special",      // k_me_walk_docs<CS, true>: a special's span is one token
+    // ids above 0xFFFF (gbpe_bpe_upload_wide)
+    "k_me_walk_wide",         // k_me_walk / k_me_walk_docs<..., WIDE = true>: every walk above on {a, b, rank, new id} slots
 };
 
 // ── context memory pool (common.h GbpePool) ───────────────────────────────

@@ -15,8 +15,8 @@
 // Both facts need every new id to be fresh: at least 256 and given by one entry of the
 // list only.  An id that was in the stream before (a byte's, an earlier entry's) lets a
 // later rank's merge feed an earlier one's pair, and has no single first and last byte;
-// gbpe_bpe_upload rejects such a list (GBPE_E_INVALID).  On every other list the result
-// is exact, the pair (0,0) included: a slot's .w, not its pid, says that it is occupied.
+// the uploads reject such a list (GBPE_E_INVALID).  On every other list the result
+// is exact, the pair (0,0) included: a slot's .w, not its key, says that it is occupied.
 //
 // k_me_walk: one lane per chunk (4096 bytes); it owns the segments that START in
 // its chunk and BPE-encodes each in place (rank lookups in an L2-resident
@@ -44,9 +44,17 @@
 // matches; the mode's mask is built per piece between them (the GPT-4 rules through the
 // document form of the pre-tokeniser, a flag at each piece's first byte), k_me_sp_mask adds
 // the spans, and k_me_walk_docs<CS, true> writes a span's id as its one token.
+//
+// Ids above 0xFFFF (gbpe_bpe_upload_wide): the rank table's slot carries both full
+// operands, {a, b, rank, new id}, and every kernel that reads the slots (the walks, me_heap) has a
+// WIDE instantiation that keys a pair by 64 bits.  The narrow instantiations keep a << 16 | b in one
+// word.  merge_table.h builds either table on the host and holds the hash both sides share.
 
 #include "common.h"
+#include "merge_table.h"
 #include "scan.h"
+
+#include <type_traits>
 
 #include <vector>
 
@@ -70,19 +78,45 @@ struct MeArena {   // per long segment at offset `off` (bytes of all long segmen
     const uint64_t* slot;   // per chunk: me_lslot(CS) offsets of the long segments starting in it
 };
 
+// merge_table.h's table.  Narrow slots (ids <= 0xFFFF) are {pid, rank, new id, occupied}, wide ones
+//  {a, b, rank, new id}; .w 0 = empty in both (the pair (0,0) is a merge like any other)
 struct MeTable {
-    const uint4* slots;   // {pid, rank, new id, occupied}; .w 0 = empty (pid 0 is the pair (0,0), a merge like any other)
+    const uint4* slots;
     uint32_t mask;
     const uint32_t* cross;   // 65536-bit: (u << 8 | v) set iff some merge joins a token ending in u to one starting with v
 };
 
+// An adjacent pair as the walks look it up and remember it.  WIDE is a template parameter of every
+// kernel that reads the slots: the narrow instantiations keep the one-word key a << 16 | b.
+template <bool WIDE>
+using me_key_t = std::conditional_t<WIDE, uint64_t, uint32_t>;
+
+template <bool WIDE>
+__device__ __forceinline__ me_key_t<WIDE> me_pair(uint32_t a, uint32_t b) {
+    return ((me_key_t<WIDE>)a << (WIDE ? 32 : 16)) | b;
+}
+
+// {_, rank, new id, _} of the pair; rank ME_NONE: no such merge.  Overloaded on the key: the narrow
+// lookup is the one the encoder has always had, the wide one tests the same word first (.w) and
+// compares both operands.  merge_table.h's host build probes the same way.
 __device__ __forceinline__ uint4 me_find(const MeTable& t, uint32_t pid) {
-    uint32_t h = gbpe_fmix32(pid) & t.mask;
+    uint32_t h = me_hash_narrow(pid) & t.mask;
     for (uint32_t p = 0; p <= t.mask; ++p) {
-        const uint32_t idx = (h + ((p * (p + 1)) >> 1)) & t.mask;
+        const uint32_t idx = me_probe(h, p, t.mask);
         const uint4 e = t.slots[idx];
         if (e.w == 0u) break;   // (tested first: an empty slot's pid reads 0, the pair (0,0))
         if (e.x == pid) return e;
+    }
+    return make_uint4(0u, ME_NONE, 0u, 0u);
+}
+
+__device__ __forceinline__ uint4 me_find(const MeTable& t, uint64_t key) {
+    const uint32_t a = (uint32_t)(key >> 32), b = (uint32_t)key;
+    uint32_t h = me_hash_wide(a, b) & t.mask;
+    for (uint32_t p = 0; p <= t.mask; ++p) {
+        const uint4 e = t.slots[me_probe(h, p, t.mask)];
+        if (e.w == 0u) break;
+        if (e.x == a && e.y == b) return make_uint4(0u, e.z, e.w, 1u);
     }
     return make_uint4(0u, ME_NONE, 0u, 0u);
 }
@@ -145,6 +179,7 @@ __global__ __launch_bounds__(ME_TPB) void k_me_long(const uint8_t* __restrict__ 
 // occurrences left to right, as the reference's one pass per merge does: a
 // merge's new pairs hold its new token, which only later ranks use.  Stale
 // entries (the pair at that position changed) are skipped on pop.
+template <bool WIDE>
 __device__ uint32_t me_heap(const uint8_t* __restrict__ in, uint32_t len, const MeTable& t, uint32_t* __restrict__ tk,
                             uint32_t* __restrict__ nx, uint32_t* __restrict__ pv, uint64_t* __restrict__ hp,
                             uint32_t* __restrict__ out) {
@@ -164,7 +199,7 @@ __device__ uint32_t me_heap(const uint8_t* __restrict__ in, uint32_t len, const 
         }
         hp[i] = key;
     };
-    auto rank_at = [&](uint32_t i, uint32_t j) -> uint4 { return me_find(t, (tk[i] << 16) | tk[j]); };
+    auto rank_at = [&](uint32_t i, uint32_t j) -> uint4 { return me_find(t, me_pair<WIDE>(tk[i], tk[j])); };
     for (uint32_t i = 0; i + 1 < len; ++i) {
         const uint4 e = rank_at(i, i + 1);
         if (e.y != ME_NONE) push(((uint64_t)e.y << 32) | i);
@@ -210,7 +245,7 @@ __device__ uint32_t me_heap(const uint8_t* __restrict__ in, uint32_t len, const 
     return cnt;
 }
 
-template <bool WORDS, uint32_t CS>
+template <bool WORDS, uint32_t CS, bool WIDE = false>
 __global__ __launch_bounds__(ME_TPB) void k_me_walk(const uint8_t* __restrict__ in, const uint8_t* __restrict__ ws,
                                                     uint64_t n, MeTable t, uint32_t* __restrict__ scratch,
                                                     uint32_t* __restrict__ counts, uint64_t* __restrict__ base,
@@ -230,22 +265,24 @@ __global__ __launch_bounds__(ME_TPB) void k_me_walk(const uint8_t* __restrict__ 
         uint32_t len = (uint32_t)(z - s);
         if (len > ME_LONG) {
             const uint64_t off = ar.slot[c * me_lslot(CS) + nlong++];
-            written += me_heap(in + s, len, t, ar.tok + off, ar.nxt + off, ar.prv + off, ar.heap + 3 * off, tok);
+            written += me_heap<WIDE>(in + s, len, t, ar.tok + off, ar.nxt + off, ar.prv + off, ar.heap + 3 * off, tok);
             s = z;
             continue;
         }
         for (uint32_t j = 0; j < len; ++j) tok[j] = in[s + j];
         while (len >= 2) {
-            uint32_t best = ME_NONE, bpid = 0, bnew = 0;
+            uint32_t best = ME_NONE;
+            me_key_t<WIDE> bpid = 0;
+            uint32_t bnew = 0;
             for (uint32_t j = 0; j + 1 < len; ++j) {
-                const uint32_t pid = (tok[j] << 16) | tok[j + 1];
+                const me_key_t<WIDE> pid = me_pair<WIDE>(tok[j], tok[j + 1]);
                 const uint4 e = me_find(t, pid);
                 if (e.y < best) { best = e.y; bpid = pid; bnew = e.z; }
             }
             if (best == ME_NONE) break;
             uint32_t w = 0, j = 0;   // this rank, every occurrence, left to right
             while (j < len) {
-                if (j + 1 < len && ((tok[j] << 16) | tok[j + 1]) == bpid) {
+                if (j + 1 < len && me_pair<WIDE>(tok[j], tok[j + 1]) == bpid) {
                     tok[w++] = bnew;
                     j += 2;
                 } else {
@@ -289,7 +326,7 @@ struct MeSp {   // the special tokens of a call (SP)
 // with ME_SP_BIT is a special's span (its other bytes are no cut, the byte after it is one): its id
 // is the segment's one token.  It belongs to the chunk that holds its first byte, and one token for
 // at least one byte keeps the tokens of a chunk behind the bytes it has consumed.
-template <uint32_t CS, bool SP = false>
+template <uint32_t CS, bool SP = false, bool WIDE = false>
 __global__ __launch_bounds__(ME_TPB) void k_me_walk_docs(const uint8_t* __restrict__ in, const uint8_t* __restrict__ ws,
                                                          uint64_t n, MeTable t, uint32_t* __restrict__ scratch,
                                                          uint32_t* __restrict__ counts, uint64_t* __restrict__ base,
@@ -327,22 +364,24 @@ __global__ __launch_bounds__(ME_TPB) void k_me_walk_docs(const uint8_t* __restri
         uint32_t len = (uint32_t)(z - s);
         if (len > ME_LONG) {
             const uint64_t off = ar.slot[c * me_lslot(CS) + nlong++];
-            written += me_heap(in + s, len, t, ar.tok + off, ar.nxt + off, ar.prv + off, ar.heap + 3 * off, tok);
+            written += me_heap<WIDE>(in + s, len, t, ar.tok + off, ar.nxt + off, ar.prv + off, ar.heap + 3 * off, tok);
             s = z;
             continue;
         }
         for (uint32_t j = 0; j < len; ++j) tok[j] = in[s + j];
         while (len >= 2) {
-            uint32_t best = ME_NONE, bpid = 0, bnew = 0;
+            uint32_t best = ME_NONE;
+            me_key_t<WIDE> bpid = 0;
+            uint32_t bnew = 0;
             for (uint32_t j = 0; j + 1 < len; ++j) {
-                const uint32_t pid = (tok[j] << 16) | tok[j + 1];
+                const me_key_t<WIDE> pid = me_pair<WIDE>(tok[j], tok[j + 1]);
                 const uint4 e = me_find(t, pid);
                 if (e.y < best) { best = e.y; bpid = pid; bnew = e.z; }
             }
             if (best == ME_NONE) break;
             uint32_t w = 0, j = 0;   // this rank, every occurrence, left to right
             while (j < len) {
-                if (j + 1 < len && ((tok[j] << 16) | tok[j + 1]) == bpid) {
+                if (j + 1 < len && me_pair<WIDE>(tok[j], tok[j + 1]) == bpid) {
                     tok[w++] = bnew;
                     j += 2;
                 } else {
@@ -452,63 +491,39 @@ struct gbpe_bpe {
     uint32_t mask = 0;
     uint32_t* cross = nullptr;
     uint32_t n_live = 0;
+    bool wide = false;   // the slots' layout, and so the walks' instantiation
 };
 
-extern "C" int gbpe_bpe_upload(gbpe_ctx* ctx, const uint32_t* merges, uint32_t n_merges, gbpe_bpe** out) {
+static_assert(sizeof(MeSlot) == sizeof(uint4), "merge_table.h's slot is the device's uint4");
+static_assert(ME_WIDE_MAX_ID == GBPE_BPE_MAX_ID, "merge_table.h's bound is the header's");
+
+// both uploads: merge_table.h's filter and table on the host, then the copies
+static int me_upload(gbpe_ctx* ctx, const uint32_t* merges, uint32_t n_merges, bool wide, gbpe_bpe** out) {
     if (!ctx || !out || (n_merges && !merges)) return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe upload: bad arguments");
     *out = nullptr;
-    // live merges: both operands exist (bytes, or created by an earlier merge), first rank of a pair
-    std::vector<uint8_t> first(1u << 16, 0), last(1u << 16, 0);
-    for (uint32_t b = 0; b < 256; ++b) first[b] = last[b] = (uint8_t)b;
-    std::vector<uint8_t> exists(1u << 16, 0), given(1u << 16, 0);   // given: the new id of an entry, live or not
-    for (uint32_t b = 0; b < 256; ++b) exists[b] = 1;
-    uint32_t slots = 16;
-    while (slots < 2u * n_merges + 16) slots <<= 1;
-    std::vector<uint4> tab(slots, make_uint4(0, 0, 0, 0));
-    std::vector<uint32_t> cross(65536 / 32, 0);
-    uint32_t live = 0;
-    for (uint32_t r = 0; r < n_merges; ++r) {
-        const uint32_t a = merges[3 * (uint64_t)r], b = merges[3 * (uint64_t)r + 1], id = merges[3 * (uint64_t)r + 2];
-        if (a > 0xFFFFu || b > 0xFFFFu || id > 0xFFFFu)
-            return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe upload: merge %u has an id above 0xFFFF", r);
-        // a new id must be fresh: one that was in the stream before (a byte, an earlier entry's) breaks
-        // "ranks in order = lowest-rank adjacent pair first", and its first / last byte would be two things
-        if (id < 256u)
-            return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe upload: merge %u has the new id %u, a byte's", r, id);
-        if (given[id])
-            return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe upload: merge %u gives the new id %u a second time", r, id);
-        given[id] = 1;
-        if (!exists[a] || !exists[b]) continue;   // an operand that does not exist yet: never fires
-        const uint32_t pid = (a << 16) | b;
-        uint32_t h = 0;
-        {   // same hash / probing as the device
-            uint32_t x = pid;
-            x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-            h = x & (slots - 1);
-        }
-        bool dup = false;
-        for (uint32_t p = 0; p < slots; ++p) {
-            const uint32_t idx = (h + ((p * (p + 1)) >> 1)) & (slots - 1);
-            if (tab[idx].w == 0) { tab[idx] = make_uint4(pid, r, id, 1); break; }
-            if (tab[idx].x == pid) { dup = true; break; }
-        }
-        if (dup) continue;   // the first rank of a pair wins (tokenizer-manager.js:30-33)
-        ++live;
-        const uint32_t k = ((uint32_t)last[a] << 8) | first[b];
-        cross[k >> 5] |= 1u << (k & 31u);
-        exists[id] = 1;   // (fresh: no earlier entry set these)
-        first[id] = first[a];
-        last[id] = last[b];
+    const uint32_t max_id = wide ? ME_WIDE_MAX_ID : ME_NARROW_MAX_ID;
+    MeHostTable tab;
+    uint32_t bad = 0, bad_id = 0;
+    switch (me_build_table(merges, n_merges, max_id, wide, &tab, &bad, &bad_id)) {
+    case ME_BUILD_OK: break;
+    case ME_BUILD_RANGE:
+        return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe upload: merge %u has an id above 0x%X", bad, max_id);
+    case ME_BUILD_BYTE_ID:
+        return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe upload: merge %u has the new id %u, a byte's", bad, bad_id);
+    case ME_BUILD_REPEATED_ID:
+        return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe upload: merge %u gives the new id %u a second time", bad, bad_id);
     }
     auto* bp = new (std::nothrow) gbpe_bpe();
     if (!bp) return gbpe_set_error(ctx, GBPE_E_OOM, "host allocation failed");
     bp->ctx = ctx;
-    bp->mask = slots - 1;
-    bp->n_live = live;
-    hipError_t e = dev_malloc(ctx, &bp->slots, slots * sizeof(uint4));
-    if (e == hipSuccess) e = dev_malloc(ctx, &bp->cross, cross.size() * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemcpy(bp->slots, tab.data(), slots * sizeof(uint4), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(bp->cross, cross.data(), cross.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    bp->mask = (uint32_t)tab.slots.size() - 1;
+    bp->n_live = tab.live;
+    bp->wide = wide;
+    const size_t slot_bytes = tab.slots.size() * sizeof(uint4), cross_bytes = tab.cross.size() * sizeof(uint32_t);
+    hipError_t e = dev_malloc(ctx, &bp->slots, slot_bytes);
+    if (e == hipSuccess) e = dev_malloc(ctx, &bp->cross, cross_bytes);
+    if (e == hipSuccess) e = hipMemcpy(bp->slots, tab.slots.data(), slot_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(bp->cross, tab.cross.data(), cross_bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         hipFree(bp->slots);
         hipFree(bp->cross);
@@ -517,6 +532,14 @@ extern "C" int gbpe_bpe_upload(gbpe_ctx* ctx, const uint32_t* merges, uint32_t n
     }
     *out = bp;
     return GBPE_OK;
+}
+
+extern "C" int gbpe_bpe_upload(gbpe_ctx* ctx, const uint32_t* merges, uint32_t n_merges, gbpe_bpe** out) {
+    return me_upload(ctx, merges, n_merges, false, out);
+}
+
+extern "C" int gbpe_bpe_upload_wide(gbpe_ctx* ctx, const uint32_t* merges, uint32_t n_merges, gbpe_bpe** out) {
+    return me_upload(ctx, merges, n_merges, true, out);
 }
 
 extern "C" void gbpe_bpe_free(gbpe_bpe* bp) {
@@ -545,24 +568,34 @@ void me_launch_long(hipStream_t s, const uint8_t* in, const uint8_t* ws, uint64_
 
 // k_me_walk; with the documents of a batch call (always the word form) k_me_walk_docs; with special
 // tokens its SP form, for one buffer too (no document bit is set then: `docs` is not read)
-template <bool WORDS, uint32_t CS>
-void me_launch_walk(hipStream_t s, const uint8_t* in, const uint8_t* ws, uint64_t n, const MeTable& t, uint32_t* scratch,
-                    uint32_t* counts, uint64_t* base, uint64_t nchunks, const MeArena& ar, const MeDocs* docs,
-                    const MeSp* sp) {
+template <bool WORDS, uint32_t CS, bool WIDE>
+void me_launch_walk_keyed(hipStream_t s, const uint8_t* in, const uint8_t* ws, uint64_t n, const MeTable& t,
+                          uint32_t* scratch, uint32_t* counts, uint64_t* base, uint64_t nchunks, const MeArena& ar,
+                          const MeDocs* docs, const MeSp* sp) {
     const dim3 grid((uint32_t)gbpe_div_up(nchunks, ME_TPB));
     if constexpr (WORDS) {
         if (sp) {
-            hipLaunchKernelGGL((k_me_walk_docs<CS, true>), grid, dim3(ME_TPB), 0, s, in, ws, n, t, scratch, counts, base,
-                               nchunks, ar, docs ? *docs : MeDocs{}, *sp);
+            hipLaunchKernelGGL((k_me_walk_docs<CS, true, WIDE>), grid, dim3(ME_TPB), 0, s, in, ws, n, t, scratch, counts,
+                               base, nchunks, ar, docs ? *docs : MeDocs{}, *sp);
             return;
         }
         if (docs) {
-            hipLaunchKernelGGL((k_me_walk_docs<CS>), grid, dim3(ME_TPB), 0, s, in, ws, n, t, scratch, counts, base, nchunks,
-                               ar, *docs, MeSp{});
+            hipLaunchKernelGGL((k_me_walk_docs<CS, false, WIDE>), grid, dim3(ME_TPB), 0, s, in, ws, n, t, scratch, counts,
+                               base, nchunks, ar, *docs, MeSp{});
             return;
         }
     }
-    hipLaunchKernelGGL((k_me_walk<WORDS, CS>), grid, dim3(ME_TPB), 0, s, in, ws, n, t, scratch, counts, base, nchunks, ar);
+    hipLaunchKernelGGL((k_me_walk<WORDS, CS, WIDE>), grid, dim3(ME_TPB), 0, s, in, ws, n, t, scratch, counts, base, nchunks,
+                       ar);
+}
+
+// (`wide`: the layout of t's slots, gbpe_bpe::wide)
+template <bool WORDS, uint32_t CS>
+void me_launch_walk(hipStream_t s, const uint8_t* in, const uint8_t* ws, uint64_t n, const MeTable& t, bool wide,
+                    uint32_t* scratch, uint32_t* counts, uint64_t* base, uint64_t nchunks, const MeArena& ar,
+                    const MeDocs* docs, const MeSp* sp) {
+    if (wide) me_launch_walk_keyed<WORDS, CS, true>(s, in, ws, n, t, scratch, counts, base, nchunks, ar, docs, sp);
+    else me_launch_walk_keyed<WORDS, CS, false>(s, in, ws, n, t, scratch, counts, base, nchunks, ar, docs, sp);
 }
 
 // the instantiation of a call: no mask at ME_CS, or the word form at cs
@@ -729,7 +762,7 @@ int me_run(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, const char* wha
     if (e == hipSuccess) {
         const MeDocs md{docs ? docs->d_doc_off : nullptr, docs ? docs->n_docs : 0, w.doc_written};
         const MeSp ms{w.mark, sp ? gbpe_specials_ids(sp) : nullptr};
-        ME_DISPATCH(me_launch_walk, words, cs, s, d_in, d_ws, n, t, w.scratch, w.counts, w.base, nchunks, ar,
+        ME_DISPATCH(me_launch_walk, words, cs, s, d_in, d_ws, n, t, bp->wide, w.scratch, w.counts, w.base, nchunks, ar,
                     docs ? &md : nullptr, sp ? &ms : nullptr);
         e = hipGetLastError();
     }

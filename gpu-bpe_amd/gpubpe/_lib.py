@@ -29,6 +29,7 @@ GBPE_TRAIN_GPT4_BOUNDARIES = 1 << 2
 
 GBPE_WORDS_NONE, GBPE_WORDS_MASK, GBPE_WORDS_HEURISTIC, GBPE_WORDS_GPT4 = 0, 1, 2, 3
 GBPE_SPECIALS_MAX, GBPE_SPECIAL_MAX_BYTES = 254, 128
+GBPE_BPE_MAX_ID = 0xFFFFFF   # gbpe_bpe_upload_wide's bound; gbpe_bpe_upload's is 0xFFFF
 
 u8p = C.POINTER(C.c_uint8)
 u32p = C.POINTER(C.c_uint32)
@@ -109,6 +110,7 @@ _SIGS = [
     ("gbpe_encode_batch_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                            C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, u64p]),
     ("gbpe_bpe_upload", C.c_int, [C.c_void_p, u32p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("gbpe_bpe_upload_wide", C.c_int, [C.c_void_p, u32p, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("gbpe_bpe_encode", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u32p, C.c_uint64, u64p]),
     ("gbpe_bpe_free", None, [C.c_void_p]),
     ("gbpe_bpe_encode_words", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, u32p,

@@ -10,7 +10,9 @@ The result is exact for every merge list whose new ids are at least 256 and dist
 (in any order; repeated pairs, the pair (0, 0) and operands created later or never
 included).  Any other list (a new id below 256, or one an earlier entry of the list
 gave) raises GpuBpeError with GBPE_E_INVALID at construction; the message names the
-merge."""
+merge.  A list that holds a value above 0xFFFF goes through gbpe_bpe_upload_wide
+(ids up to GBPE_BPE_MAX_ID = 0xFFFFFF: the 100K to 200K vocabularies); every encode
+call is the same, and a value above that bound is GBPE_E_INVALID too."""
 from __future__ import annotations
 
 import ctypes as C
@@ -93,10 +95,17 @@ class MergeEncoder:
         self._sp = None
         self.special_tokens = checked_special_tokens(special_tokens) if special_tokens is not None else None
         lib = _lib.load()
+        for r, m in enumerate(self._merges):   # (what does not fit a u32 cannot reach the library's own check)
+            if not all(0 <= int(v) <= 0xFFFFFFFF for v in m):
+                raise _lib.GpuBpeError(_lib.GBPE_E_INVALID, f"bpe upload: merge {r} has an id above "
+                                       f"0x{_lib.GBPE_BPE_MAX_ID:X} (status {_lib.GBPE_E_INVALID})")
         arr = np.ascontiguousarray(np.asarray(self._merges, dtype=np.uint32).reshape(-1, 3))
+        # ids above 0xFFFF take the wide rank table (gbpe_bpe_upload_wide, up to GBPE_BPE_MAX_ID)
+        self.wide = bool(arr.size) and int(arr.max()) > 0xFFFF
+        upload = lib.gbpe_bpe_upload_wide if self.wide else lib.gbpe_bpe_upload
         h = C.c_void_p()
-        _lib.check(lib.gbpe_bpe_upload(engine.device, arr.ctypes.data_as(_lib.u32p), arr.shape[0], C.byref(h)),
-                   engine.device, "bpe upload")
+        _lib.check(upload(engine.device, arr.ctypes.data_as(_lib.u32p), arr.shape[0], C.byref(h)), engine.device,
+                   "bpe upload")
         self._h = h
         if self.special_tokens is not None:
             raw = np.frombuffer(b"".join(k for k, _ in self.special_tokens), dtype=np.uint8)

@@ -529,7 +529,8 @@ void specials_finalize(napi_env, void* data, void*) {
     delete s;
 }
 
-napi_value BpeUpload(napi_env env, napi_callback_info info) {
+// bpeUpload (ids up to 0xFFFF) and bpeUploadWide (up to GBPE_BPE_MAX_ID): the same handle
+napi_value bpe_upload(napi_env env, napi_callback_info info, bool wide) {
     size_t argc = 2;
     napi_value argv[2];
     NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
@@ -537,12 +538,14 @@ napi_value BpeUpload(napi_env env, napi_callback_info info) {
     const uint32_t* m = nullptr;
     size_t nm = 0;
     if (!ctx_usable(c) || argc < 2 || !get_u32s(env, argv[1], &m, &nm)) {
-        napi_throw_type_error(env, nullptr, "bpeUpload(ctx, merges: Uint32Array [a,b,id]*)");
+        napi_throw_type_error(env, nullptr, wide ? "bpeUploadWide(ctx, merges: Uint32Array [a,b,id]*)"
+                                                 : "bpeUpload(ctx, merges: Uint32Array [a,b,id]*)");
         return nullptr;
     }
     auto* b = new Bpe();
     std::unique_lock<std::mutex> g(c->mu);
-    int rc = gbpe_bpe_upload(c->ctx, m, (uint32_t)(nm / 3), &b->bpe);
+    int rc = wide ? gbpe_bpe_upload_wide(c->ctx, m, (uint32_t)(nm / 3), &b->bpe)
+                  : gbpe_bpe_upload(c->ctx, m, (uint32_t)(nm / 3), &b->bpe);
     g.unlock();
     if (rc == GBPE_OK) {
         b->owner = c;
@@ -556,6 +559,9 @@ napi_value BpeUpload(napi_env env, napi_callback_info info) {
     NAPI_CALL(env, napi_create_external(env, b, bpe_finalize, nullptr, &ext));
     return ext;
 }
+
+napi_value BpeUpload(napi_env env, napi_callback_info info) { return bpe_upload(env, info, false); }
+napi_value BpeUploadWide(napi_env env, napi_callback_info info) { return bpe_upload(env, info, true); }
 
 napi_value BpeEncode(napi_env env, napi_callback_info info) {
     size_t argc = 3;
@@ -1198,6 +1204,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"trainerDestroy", nullptr, TrainerDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"trieUpload", nullptr, TrieUpload, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"bpeUpload", nullptr, BpeUpload, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"bpeUploadWide", nullptr, BpeUploadWide, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"bpeEncode", nullptr, BpeEncode, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"bpeEncodeWords", nullptr, BpeEncodeWords, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"trieFree", nullptr, TrieFree, nullptr, nullptr, nullptr, napi_default, nullptr},

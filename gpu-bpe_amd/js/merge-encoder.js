@@ -14,7 +14,8 @@
  * Exact for every merge list whose new ids are at least 256 and distinct (any order,
  * repeated pairs, the pair (0, 0) and operands created later or never included); a
  * new id below 256 or given twice makes the constructor throw (GBPE_E_INVALID, the
- * message names the merge).
+ * message names the merge).  A list that holds an id above 0xFFFF is uploaded through
+ * gbpe_bpe_upload_wide (ids up to 0xFFFFFF); every call is the same.
  * Node 12 syntax.
  */
 import { native } from './native.js';
@@ -69,8 +70,18 @@ export class MergeEncoder {
         this.specialTokens = opts && opts.specialTokens ? checkedSpecialTokens(opts.specialTokens) : null;
         const merges = model.merges || [];
         const flat = new Uint32Array(merges.length * 3);
-        merges.forEach(function (m, i) { flat[3 * i] = m[0]; flat[3 * i + 1] = m[1]; flat[3 * i + 2] = m[2]; });
-        this._h = native().bpeUpload(engine.device, flat);
+        // ids above 0xFFFF take the wide rank table (gbpe_bpe_upload_wide, up to 0xFFFFFF); what no u32 holds
+        // goes in as 0xFFFFFFFF, so that the library rejects it and names the merge
+        let wide = false;
+        merges.forEach(function (m, i) {
+            for (let k = 0; k < 3; k++) {
+                const v = Number.isInteger(m[k]) && m[k] >= 0 && m[k] <= 0xFFFFFFFF ? m[k] : 0xFFFFFFFF;
+                if (v > 0xFFFF) wide = true;
+                flat[3 * i + k] = v;
+            }
+        });
+        this.wide = wide;
+        this._h = wide ? native().bpeUploadWide(engine.device, flat) : native().bpeUpload(engine.device, flat);
         if (this.specialTokens !== null) {
             const flatSp = flattenDocuments(this.specialTokens.map(function (e) { return e.bytes; }));
             const ids = Uint32Array.from(this.specialTokens.map(function (e) { return e.id; }));

@@ -392,6 +392,15 @@ int  gbpe_bpe_upload(gbpe_ctx* ctx, const uint32_t* merges, uint32_t n_merges, g
 int  gbpe_bpe_encode(gbpe_ctx* ctx, gbpe_bpe* bpe, const uint8_t* bytes, uint64_t n, uint32_t* out, uint64_t out_cap,
                      uint64_t* n_out);
 void gbpe_bpe_free(gbpe_bpe* bpe);
+/* The same for models with ids above 0xFFFF: every a, b and new id at
+ * most GBPE_BPE_MAX_ID, all else as gbpe_bpe_upload (fresh new ids, the first rank
+ * of a repeated pair, operands that do not exist yet, *out = NULL and the merge's
+ * index in gbpe_last_error on GBPE_E_INVALID).  The handle is a gbpe_bpe like any
+ * other: every gbpe_bpe_encode* call takes it, and gbpe_bpe_free releases it.  The
+ * rank table keys a pair by both full operands; a list that fits gbpe_bpe_upload
+ * gives the same tokens through either call. */
+#define GBPE_BPE_MAX_ID 0xFFFFFFu   /* 2^24 - 1 */
+int  gbpe_bpe_upload_wide(gbpe_ctx* ctx, const uint32_t* merges, uint32_t n_merges, gbpe_bpe** out);
 
 /* Merge-rank encode within word boundaries: pre-tokenise, then BPE
  * inside each word — what a model trained with word starts means.  word_starts is
