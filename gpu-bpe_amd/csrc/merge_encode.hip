@@ -18,37 +18,39 @@
 // the uploads reject such a list (GBPE_E_INVALID).  On every other list the result
 // is exact, the pair (0,0) included: a slot's .w, not its key, says that it is occupied.
 //
-// k_me_walk: one lane per chunk (4096 bytes); it owns the segments that START in
-// its chunk and BPE-encodes each in place (rank lookups in an L2-resident
-// open-addressing table).  Chunk counts → scan.h two-level scan → k_me_compact.
-// A segment longer than ME_LONG bytes (CJK paragraphs, base64, minified code:
-// no cut for a long stretch) would cost its lane one full pass per rank
-// applied; it is encoded with a rank-ordered heap over a linked list instead
-// (me_heap: O(len log len), same order: lowest rank first, leftmost first),
-// in an arena k_me_long sized and laid out beforehand.
+// The pipeline (me_run): the mask of the call → k_me_long → the walk → scan.h's two-level scan of the
+// chunks' token counts → k_me_compact (and k_me_tok_off, the documents' token offsets).
 //
-// Word-bounded encode (gbpe_bpe_encode_words*): a byte mask of word
-// starts adds cuts, so that the result is the concatenation of each word's own
-// encoding.  k_me_long and k_me_walk take the predicate (WORDS) and the chunk
-// size (CS) as template parameters: <false, ME_CS> is the whole-string encoder,
-// <true, CS> cuts at ws[i] != 0 as well.  Words are a few bytes long, so there a
-// lane's range and not its segments sets the serial length: the word
-// instantiations exist at 4096, 1024 and 256 bytes per lane (GBPE_DEBUG me_cs).
+// The walk (me_walk): one lane per chunk of CS bytes.  A lane owns the segments that START in its
+// chunk (the last may run past the chunk's end), copies each into scratch at the place of its bytes
+// and BPE-encodes it there: me_short, one pass per rank applied, rank lookups in an L2-resident
+// open-addressing table.  The walk exists once; five template switches make its instantiations:
+//   WORDS  a byte mask of word starts adds cuts, so that the result is the
+//          concatenation of each word's own encoding; without it the whole string is one text.
+//   CS     4096 without a mask.  Words are a few bytes long, so with one a lane's range and not
+//          its segments sets the serial length: 4096, 1024 or 256 (GBPE_DEBUG me_cs; ME_CS_WORDS ships).
+//   DOCS   many documents in one call: a document start is one more cut, and the lane
+//          notes how many tokens it had written at each; k_me_tok_off adds the chunk's prefix.
+//   SP     special tokens: special.hip marks the accepted matches, and a match's span
+//          is one segment whose one token is the special's id.
+//   WIDE   ids above 0xFFFF: the table's slot carries both full operands,
+//          {a, b, rank, new id}, and a pair is keyed by 64 bits; the narrow form keeps a << 16 | b
+//          in one word.  merge_table.h builds either table on the host and holds the hash both
+//          sides share.  me_heap is the other reader of the slots and takes the same switch.
+// Two __global__ symbols carry it: k_me_walk<WORDS, CS, WIDE> (no DOCS, no SP) and
+// k_me_walk_docs<CS, SP, WIDE> (WORDS and DOCS: a call with special tokens is launched as a batch
+// of no documents).  me_launch is the one place that picks an instantiation.
 //
-// Many documents in one call (gbpe_bpe_encode_words_batch*): a document
-// start is one more cut, so the tokens are the word walk's under the mask `the mode's
-// per-document mask | document starts`; k_me_walk_docs also notes how many tokens its
-// lane had written at each document start, and k_me_tok_off adds the chunk's prefix.
+// The long-segment arena: a segment longer than ME_LONG bytes (CJK paragraphs, base64, minified
+// code: no cut for a long stretch) would cost its lane one full pass per rank applied; it is encoded
+// with a rank-ordered heap over a linked list instead (me_heap: O(len log len), same order: lowest
+// rank first, leftmost first).  k_me_long runs before the walk, finds those segments with the walk's
+// own cut predicate (me_cut), and gives each an offset into an arena sized by their total length.
 //
-// Special tokens (gbpe_bpe_encode_special*): special.hip marks the accepted
-// matches; the mode's mask is built per piece between them (the GPT-4 rules through the
-// document form of the pre-tokeniser, a flag at each piece's first byte), k_me_sp_mask adds
-// the spans, and k_me_walk_docs<CS, true> writes a span's id as its one token.
-//
-// Ids above 0xFFFF (gbpe_bpe_upload_wide): the rank table's slot carries both full
-// operands, {a, b, rank, new id}, and every kernel that reads the slots (the walks, me_heap) has a
-// WIDE instantiation that keys a pair by 64 bits.  The narrow instantiations keep a << 16 | b in one
-// word.  merge_table.h builds either table on the host and holds the hash both sides share.
+// The mask bits: a caller's mask or a mode's is 0 / nonzero per byte.  A batch call and a call with
+// special tokens build their own (me_mask): bit 0 a word start within a document or a piece between
+// specials, ME_DOC_BIT a document start, ME_SP_BIT / ME_SPIN_BIT a special's first / other bytes
+// (k_me_sp_mask).  Any nonzero byte but ME_SPIN_BIT alone is a cut.
 
 #include "common.h"
 #include "merge_table.h"
@@ -127,28 +129,19 @@ __device__ __forceinline__ uint4 me_find(const MeTable& t, uint64_t key) {
 constexpr uint32_t ME_DOC_BIT = 2u, ME_SP_BIT = 4u, ME_SPIN_BIT = 8u;
 
 // a segment starts at byte i: a word start (WORDS), or no merge crosses (i - 1, i).  SP: never
-// inside a special, whatever the pair says — a lane whose chunk begins there must skip to its end
+// inside a special, whatever the pair says — a lane whose chunk begins there must skip to its end.
+// With `w`, the mask byte goes back to the caller: the walk tests the byte of a segment's start
+// without loading it again.  This is the one predicate of k_me_long and of the walk: k_me_long's
+// arena offsets are the walk's only if both cut at the same bytes, so neither gets a form of its own.
 template <bool WORDS, bool SP = false>
 __device__ __forceinline__ bool me_cut(const uint8_t* __restrict__ in, const uint8_t* __restrict__ ws, const MeTable& t,
-                                       uint64_t i) {
+                                       uint64_t i, uint32_t* w = nullptr) {
+    if (w) *w = ws[i];   // (before the test of i: the walk wants the byte at 0 as well)
     if (i == 0) return true;
-    if (SP) {
-        const uint32_t w = ws[i];
-        if (w) return w != ME_SPIN_BIT;   // (k_me_sp_mask leaves that bit alone on a span's inner bytes)
-    } else if (WORDS && ws[i] != 0) {
-        return true;
+    if (WORDS) {
+        const uint32_t m = w ? *w : ws[i];
+        if (m) return !SP || m != ME_SPIN_BIT;   // (k_me_sp_mask leaves that bit alone on a span's inner bytes)
     }
-    const uint32_t k = ((uint32_t)in[i - 1] << 8) | in[i];
-    return ((t.cross[k >> 5] >> (k & 31u)) & 1u) == 0u;
-}
-
-// me_cut<true, true> that hands back the mask byte it read: the walk tests the byte of a segment's
-// start without loading it again
-__device__ __forceinline__ bool me_cut_sp(const uint8_t* __restrict__ in, const uint8_t* __restrict__ ws, const MeTable& t,
-                                          uint64_t i, uint32_t* w) {
-    *w = ws[i];
-    if (i == 0) return true;
-    if (*w) return *w != ME_SPIN_BIT;
     const uint32_t k = ((uint32_t)in[i - 1] << 8) | in[i];
     return ((t.cross[k >> 5] >> (k & 31u)) & 1u) == 0u;
 }
@@ -245,56 +238,35 @@ __device__ uint32_t me_heap(const uint8_t* __restrict__ in, uint32_t len, const 
     return cnt;
 }
 
-template <bool WORDS, uint32_t CS, bool WIDE = false>
-__global__ __launch_bounds__(ME_TPB) void k_me_walk(const uint8_t* __restrict__ in, const uint8_t* __restrict__ ws,
-                                                    uint64_t n, MeTable t, uint32_t* __restrict__ scratch,
-                                                    uint32_t* __restrict__ counts, uint64_t* __restrict__ base,
-                                                    uint64_t nchunks, MeArena ar) {
-    const uint64_t c = (uint64_t)blockIdx.x * ME_TPB + threadIdx.x;
-    if (c >= nchunks) return;
-    const uint64_t lo = c * CS, hi = min(lo + CS, n);
-    uint64_t s = lo;
-    while (s < hi && !me_cut<WORDS>(in, ws, t, s)) ++s;   // first segment start in the chunk
-    base[c] = s;
-    const uint64_t b0 = s;   // this chunk's tokens go to scratch[b0 ...]: never past the bytes consumed
-    uint32_t written = 0, nlong = 0;
-    while (s < hi) {
-        uint64_t z = s + 1;
-        while (z < n && !me_cut<WORDS>(in, ws, t, z)) ++z;   // the segment [s, z) may run past hi
-        uint32_t* tok = scratch + b0 + written;
-        uint32_t len = (uint32_t)(z - s);
-        if (len > ME_LONG) {
-            const uint64_t off = ar.slot[c * me_lslot(CS) + nlong++];
-            written += me_heap<WIDE>(in + s, len, t, ar.tok + off, ar.nxt + off, ar.prv + off, ar.heap + 3 * off, tok);
-            s = z;
-            continue;
+// one short segment (at most ME_LONG tokens) in place: the lowest rank among its adjacent pairs,
+// every occurrence, left to right, until no pair has a rank.  Returns the new length.
+// The shape of the two loops is a measured one ("The short-segment loop"): as a function,
+// the text the kernels used to hold compiled to two more scalar instructions in the second loop and
+// ran 0.6 - 1.9 % slower at 1024 and 256 bytes per lane; this form is not slower on any leg.
+template <bool WIDE>
+__device__ __forceinline__ uint32_t me_short(uint32_t* tok, uint32_t len, const MeTable& t) {
+    if (len >= 2) do {
+        uint32_t best = ME_NONE;
+        me_key_t<WIDE> bpid = 0;
+        uint32_t bnew = 0;
+        for (uint32_t j = 0; j + 1 < len; ++j) {
+            const me_key_t<WIDE> pid = me_pair<WIDE>(tok[j], tok[j + 1]);
+            const uint4 e = me_find(t, pid);
+            if (e.y < best) { best = e.y; bpid = pid; bnew = e.z; }
         }
-        for (uint32_t j = 0; j < len; ++j) tok[j] = in[s + j];
-        while (len >= 2) {
-            uint32_t best = ME_NONE;
-            me_key_t<WIDE> bpid = 0;
-            uint32_t bnew = 0;
-            for (uint32_t j = 0; j + 1 < len; ++j) {
-                const me_key_t<WIDE> pid = me_pair<WIDE>(tok[j], tok[j + 1]);
-                const uint4 e = me_find(t, pid);
-                if (e.y < best) { best = e.y; bpid = pid; bnew = e.z; }
+        if (best == ME_NONE) break;
+        uint32_t w = 0, j = 0;
+        while (j < len) {
+            uint32_t v = tok[j++];
+            if (j < len && me_pair<WIDE>(v, tok[j]) == bpid) {
+                v = bnew;
+                ++j;
             }
-            if (best == ME_NONE) break;
-            uint32_t w = 0, j = 0;   // this rank, every occurrence, left to right
-            while (j < len) {
-                if (j + 1 < len && me_pair<WIDE>(tok[j], tok[j + 1]) == bpid) {
-                    tok[w++] = bnew;
-                    j += 2;
-                } else {
-                    tok[w++] = tok[j++];
-                }
-            }
-            len = w;
+            tok[w++] = v;   // (w < j: behind what is still to be read)
         }
-        written += len;
-        s = z;
-    }
-    counts[c] = written;
+        len = w;
+    } while (len >= 2);
+    return len;
 }
 
 // the first document whose offset is p (p is one of doc_off[0, n_docs))
@@ -322,78 +294,68 @@ struct MeSp {   // the special tokens of a call (SP)
     const uint32_t* ids;   // by index
 };
 
-// k_me_walk<true, CS> + the tokens written before each document start.  SP: a segment that begins
-// with ME_SP_BIT is a special's span (its other bytes are no cut, the byte after it is one): its id
-// is the segment's one token.  It belongs to the chunk that holds its first byte, and one token for
-// at least one byte keeps the tokens of a chunk behind the bytes it has consumed.
-template <uint32_t CS, bool SP = false, bool WIDE = false>
-__global__ __launch_bounds__(ME_TPB) void k_me_walk_docs(const uint8_t* __restrict__ in, const uint8_t* __restrict__ ws,
-                                                         uint64_t n, MeTable t, uint32_t* __restrict__ scratch,
-                                                         uint32_t* __restrict__ counts, uint64_t* __restrict__ base,
-                                                         uint64_t nchunks, MeArena ar, MeDocs docs, MeSp sp) {
+// The walk: one lane per chunk of CS bytes encodes the segments that start in its chunk, each in
+// place in scratch, and counts its tokens.  DOCS: also the tokens written before each document
+// start.  SP: a segment that begins with ME_SP_BIT is a special's span (its other bytes are no cut,
+// the byte after it is one): its id is the segment's one token.  It belongs to the chunk that holds
+// its first byte, and one token for at least one byte keeps the tokens of a chunk behind the bytes
+// it has consumed.
+template <bool WORDS, uint32_t CS, bool DOCS, bool SP, bool WIDE>
+__device__ __forceinline__ void me_walk(const uint8_t* __restrict__ in, const uint8_t* __restrict__ ws, uint64_t n,
+                                        const MeTable& t, uint32_t* __restrict__ scratch, uint32_t* __restrict__ counts,
+                                        uint64_t* __restrict__ base, uint64_t nchunks, const MeArena& ar,
+                                        const MeDocs& docs, const MeSp& sp) {
     const uint64_t c = (uint64_t)blockIdx.x * ME_TPB + threadIdx.x;
     if (c >= nchunks) return;
     const uint64_t lo = c * CS, hi = min(lo + CS, n);
     uint64_t s = lo;
     uint32_t ws_s = 0, ws_z = 0;   // (SP) the mask bytes at s and at z
-    if constexpr (SP) {
-        while (s < hi && !me_cut_sp(in, ws, t, s, &ws_s)) ++s;
-    } else {
-        while (s < hi && !me_cut<true>(in, ws, t, s)) ++s;   // first segment start in the chunk
-    }
+    while (s < hi && !me_cut<WORDS, SP>(in, ws, t, s, SP ? &ws_s : nullptr)) ++s;   // first segment start in the chunk
     base[c] = s;
     const uint64_t b0 = s;   // this chunk's tokens go to scratch[b0 ...]: never past the bytes consumed
     uint32_t written = 0, nlong = 0;
     while (s < hi) {
         uint64_t z = s + 1;
-        if constexpr (SP) {
-            while (z < n && !me_cut_sp(in, ws, t, z, &ws_z)) ++z;
-        } else {
-            while (z < n && !me_cut<true>(in, ws, t, z)) ++z;   // the segment [s, z) may run past hi
+        while (z < n && !me_cut<WORDS, SP>(in, ws, t, z, SP ? &ws_z : nullptr)) ++z;   // the segment [s, z) may run past hi
+        if constexpr (DOCS) {
+            const uint32_t w0 = SP ? ws_s : ws[s];
+            ws_s = ws_z;   // (z == n: not read, and the loop ends)
+            if (w0 & ME_DOC_BIT) docs.written[me_first_doc(docs.doc_off, docs.n_docs, s)] = written;
+            if (SP && (w0 & ME_SP_BIT)) {
+                scratch[b0 + written++] = sp.ids[sp.mark[s] - 1u];
+                s = z;
+                continue;
+            }
         }
-        const uint32_t w0 = SP ? ws_s : ws[s];
-        ws_s = ws_z;   // (z == n: not read, and the loop ends)
-        if (w0 & ME_DOC_BIT) docs.written[me_first_doc(docs.doc_off, docs.n_docs, s)] = written;
         uint32_t* tok = scratch + b0 + written;
-        if (SP && (w0 & ME_SP_BIT)) {
-            tok[0] = sp.ids[sp.mark[s] - 1u];
-            ++written;
-            s = z;
-            continue;
-        }
-        uint32_t len = (uint32_t)(z - s);
+        const uint32_t len = (uint32_t)(z - s);
         if (len > ME_LONG) {
             const uint64_t off = ar.slot[c * me_lslot(CS) + nlong++];
             written += me_heap<WIDE>(in + s, len, t, ar.tok + off, ar.nxt + off, ar.prv + off, ar.heap + 3 * off, tok);
-            s = z;
-            continue;
+        } else {
+            for (uint32_t j = 0; j < len; ++j) tok[j] = in[s + j];
+            written += me_short<WIDE>(tok, len, t);
         }
-        for (uint32_t j = 0; j < len; ++j) tok[j] = in[s + j];
-        while (len >= 2) {
-            uint32_t best = ME_NONE;
-            me_key_t<WIDE> bpid = 0;
-            uint32_t bnew = 0;
-            for (uint32_t j = 0; j + 1 < len; ++j) {
-                const me_key_t<WIDE> pid = me_pair<WIDE>(tok[j], tok[j + 1]);
-                const uint4 e = me_find(t, pid);
-                if (e.y < best) { best = e.y; bpid = pid; bnew = e.z; }
-            }
-            if (best == ME_NONE) break;
-            uint32_t w = 0, j = 0;   // this rank, every occurrence, left to right
-            while (j < len) {
-                if (j + 1 < len && me_pair<WIDE>(tok[j], tok[j + 1]) == bpid) {
-                    tok[w++] = bnew;
-                    j += 2;
-                } else {
-                    tok[w++] = tok[j++];
-                }
-            }
-            len = w;
-        }
-        written += len;
         s = z;
     }
     counts[c] = written;
+}
+
+// The walk's two symbols: without and with the documents' and specials' arguments.
+template <bool WORDS, uint32_t CS, bool WIDE = false>
+__global__ __launch_bounds__(ME_TPB) void k_me_walk(const uint8_t* __restrict__ in, const uint8_t* __restrict__ ws,
+                                                    uint64_t n, MeTable t, uint32_t* __restrict__ scratch,
+                                                    uint32_t* __restrict__ counts, uint64_t* __restrict__ base,
+                                                    uint64_t nchunks, MeArena ar) {
+    me_walk<WORDS, CS, false, false, WIDE>(in, ws, n, t, scratch, counts, base, nchunks, ar, MeDocs{}, MeSp{});
+}
+
+template <uint32_t CS, bool SP = false, bool WIDE = false>
+__global__ __launch_bounds__(ME_TPB) void k_me_walk_docs(const uint8_t* __restrict__ in, const uint8_t* __restrict__ ws,
+                                                         uint64_t n, MeTable t, uint32_t* __restrict__ scratch,
+                                                         uint32_t* __restrict__ counts, uint64_t* __restrict__ base,
+                                                         uint64_t nchunks, MeArena ar, MeDocs docs, MeSp sp) {
+    me_walk<true, CS, true, SP, WIDE>(in, ws, n, t, scratch, counts, base, nchunks, ar, docs, sp);
 }
 
 // the caller's mask as 0 / 1 (any alignment), four bytes per lane: bit 1 stays free for the document starts
@@ -553,60 +515,6 @@ extern "C" void gbpe_bpe_free(gbpe_bpe* bp) {
 
 namespace {
 
-template <bool WORDS, uint32_t CS>
-void me_launch_long(hipStream_t s, const uint8_t* in, const uint8_t* ws, uint64_t n, const MeTable& t,
-                    unsigned long long* total, uint64_t* slot, uint64_t nchunks, bool special) {
-    const dim3 grid((uint32_t)gbpe_div_up(nchunks, ME_TPB));
-    if constexpr (WORDS) {
-        if (special) {   // (the same cuts as the special walk)
-            hipLaunchKernelGGL((k_me_long<true, CS, true>), grid, dim3(ME_TPB), 0, s, in, ws, n, t, total, slot, nchunks);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((k_me_long<WORDS, CS>), grid, dim3(ME_TPB), 0, s, in, ws, n, t, total, slot, nchunks);
-}
-
-// k_me_walk; with the documents of a batch call (always the word form) k_me_walk_docs; with special
-// tokens its SP form, for one buffer too (no document bit is set then: `docs` is not read)
-template <bool WORDS, uint32_t CS, bool WIDE>
-void me_launch_walk_keyed(hipStream_t s, const uint8_t* in, const uint8_t* ws, uint64_t n, const MeTable& t,
-                          uint32_t* scratch, uint32_t* counts, uint64_t* base, uint64_t nchunks, const MeArena& ar,
-                          const MeDocs* docs, const MeSp* sp) {
-    const dim3 grid((uint32_t)gbpe_div_up(nchunks, ME_TPB));
-    if constexpr (WORDS) {
-        if (sp) {
-            hipLaunchKernelGGL((k_me_walk_docs<CS, true, WIDE>), grid, dim3(ME_TPB), 0, s, in, ws, n, t, scratch, counts,
-                               base, nchunks, ar, docs ? *docs : MeDocs{}, *sp);
-            return;
-        }
-        if (docs) {
-            hipLaunchKernelGGL((k_me_walk_docs<CS, false, WIDE>), grid, dim3(ME_TPB), 0, s, in, ws, n, t, scratch, counts,
-                               base, nchunks, ar, *docs, MeSp{});
-            return;
-        }
-    }
-    hipLaunchKernelGGL((k_me_walk<WORDS, CS, WIDE>), grid, dim3(ME_TPB), 0, s, in, ws, n, t, scratch, counts, base, nchunks,
-                       ar);
-}
-
-// (`wide`: the layout of t's slots, gbpe_bpe::wide)
-template <bool WORDS, uint32_t CS>
-void me_launch_walk(hipStream_t s, const uint8_t* in, const uint8_t* ws, uint64_t n, const MeTable& t, bool wide,
-                    uint32_t* scratch, uint32_t* counts, uint64_t* base, uint64_t nchunks, const MeArena& ar,
-                    const MeDocs* docs, const MeSp* sp) {
-    if (wide) me_launch_walk_keyed<WORDS, CS, true>(s, in, ws, n, t, scratch, counts, base, nchunks, ar, docs, sp);
-    else me_launch_walk_keyed<WORDS, CS, false>(s, in, ws, n, t, scratch, counts, base, nchunks, ar, docs, sp);
-}
-
-// the instantiation of a call: no mask at ME_CS, or the word form at cs
-#define ME_DISPATCH(fn, words, cs, ...)                          \
-    do {                                                         \
-        if (!(words)) fn<false, ME_CS>(__VA_ARGS__);             \
-        else if ((cs) == 4096u) fn<true, 4096u>(__VA_ARGS__);    \
-        else if ((cs) == 1024u) fn<true, 1024u>(__VA_ARGS__);    \
-        else fn<true, 256u>(__VA_ARGS__);                        \
-    } while (0)
-
 inline uint64_t up16(uint64_t x) { return (x + 15) & ~15ull; }
 
 struct MeWork {   // the device arrays of one call, each 16-byte aligned inside one pooled block
@@ -659,6 +567,55 @@ hipError_t me_arena(gbpe_ctx* ctx, GbpeArray<uint8_t>& blk, uint64_t long_total,
     ar->prv = ar->nxt + long_total;
     return hipSuccess;
 }
+
+// The kernels of a call, chosen here and nowhere else.  Without an arena (`ar` null: this kernel's
+// total sizes it) k_me_long, with special tokens under the SP predicate, the cuts of the SP walk.
+// With one, the walk: k_me_walk; with the documents of a batch call (always the word form)
+// k_me_walk_docs; with special tokens its SP form, for one buffer too (no document bit is set then:
+// `docs` is not read).  `wide`: the layout of t's slots, gbpe_bpe::wide.
+template <bool WORDS, uint32_t CS>
+void me_launch(hipStream_t s, const uint8_t* in, const uint8_t* ws, uint64_t n, const MeTable& t, bool wide,
+               const MeWork& w, uint64_t nchunks, const MeArena* ar, const MeDocs* docs, const MeSp* sp) {
+    const dim3 grid((uint32_t)gbpe_div_up(nchunks, ME_TPB)), tpb(ME_TPB);
+    if (!ar) {
+        if constexpr (WORDS) {
+            if (sp) {
+                hipLaunchKernelGGL((k_me_long<true, CS, true>), grid, tpb, 0, s, in, ws, n, t, w.back, w.slot, nchunks);
+                return;
+            }
+        }
+        hipLaunchKernelGGL((k_me_long<WORDS, CS>), grid, tpb, 0, s, in, ws, n, t, w.back, w.slot, nchunks);
+        return;
+    }
+    auto walk = [&](auto wide_c) {
+        constexpr bool WIDE = decltype(wide_c)::value;
+        if constexpr (WORDS) {
+            if (sp) {
+                hipLaunchKernelGGL((k_me_walk_docs<CS, true, WIDE>), grid, tpb, 0, s, in, ws, n, t, w.scratch, w.counts,
+                                   w.base, nchunks, *ar, docs ? *docs : MeDocs{}, *sp);
+                return;
+            }
+            if (docs) {
+                hipLaunchKernelGGL((k_me_walk_docs<CS, false, WIDE>), grid, tpb, 0, s, in, ws, n, t, w.scratch, w.counts,
+                                   w.base, nchunks, *ar, *docs, MeSp{});
+                return;
+            }
+        }
+        hipLaunchKernelGGL((k_me_walk<WORDS, CS, WIDE>), grid, tpb, 0, s, in, ws, n, t, w.scratch, w.counts, w.base,
+                           nchunks, *ar);
+    };
+    if (wide) walk(std::true_type{});
+    else walk(std::false_type{});
+}
+
+// the instantiation of a call: no mask at ME_CS, or the word form at cs
+#define ME_DISPATCH(words, cs, ...)                                     \
+    do {                                                                \
+        if (!(words)) me_launch<false, ME_CS>(__VA_ARGS__);             \
+        else if ((cs) == 4096u) me_launch<true, 4096u>(__VA_ARGS__);    \
+        else if ((cs) == 1024u) me_launch<true, 1024u>(__VA_ARGS__);    \
+        else me_launch<true, 256u>(__VA_ARGS__);                        \
+    } while (0)
 
 struct MeDocJob {   // the documents of a batch call, n_docs > 0
     const uint64_t* d_doc_off;   // [0, n_docs]
@@ -744,9 +701,13 @@ int me_run(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, const char* wha
     }
     GBPE_HIP(ctx, hipEventRecord(ctx->ev[1], s));
     // long segments: their total length sizes the heap arena (none: no arena)
+    const MeDocs md{docs ? docs->d_doc_off : nullptr, docs ? docs->n_docs : 0, w.doc_written};
+    const MeSp ms{w.mark, sp ? gbpe_specials_ids(sp) : nullptr};
+    const MeDocs* pd = docs ? &md : nullptr;
+    const MeSp* ps = sp ? &ms : nullptr;
     hipError_t e = docs || sp ? hipSuccess : hipMemsetAsync(w.back, 0, cell, s);
     if (e == hipSuccess) {
-        ME_DISPATCH(me_launch_long, words, cs, s, d_in, d_ws, n, t, w.back, w.slot, nchunks, sp != nullptr);
+        ME_DISPATCH(words, cs, s, d_in, d_ws, n, t, bp->wide, w, nchunks, nullptr, pd, ps);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipEventRecord(ctx->ev[2], s);
@@ -760,10 +721,7 @@ int me_run(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, const char* wha
     if (e == hipSuccess) e = me_arena(ctx, arena, back[0], w.slot, &ar);
     if (e == hipSuccess) e = hipEventRecord(ctx->ev[3], s);
     if (e == hipSuccess) {
-        const MeDocs md{docs ? docs->d_doc_off : nullptr, docs ? docs->n_docs : 0, w.doc_written};
-        const MeSp ms{w.mark, sp ? gbpe_specials_ids(sp) : nullptr};
-        ME_DISPATCH(me_launch_walk, words, cs, s, d_in, d_ws, n, t, bp->wide, w.scratch, w.counts, w.base, nchunks, ar,
-                    docs ? &md : nullptr, sp ? &ms : nullptr);
+        ME_DISPATCH(words, cs, s, d_in, d_ws, n, t, bp->wide, w, nchunks, &ar, pd, ps);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipEventRecord(ctx->ev[4], s);
@@ -815,57 +773,90 @@ int me_words_check(gbpe_ctx* ctx, const void* word_starts, uint32_t mode) {
 
 }  // namespace
 
-// The four entry points, each with and without a special table (`special`: sp must be one)
+// ── the entry points: one buffer or many documents (`batch`), each with and without a
+//    special table (`special`: sp must be one), on device or on host buffers ──
 namespace {
 
-int me_words_device(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, bool special, const void* d_bytes, uint64_t n,
-                    const void* d_word_starts, uint32_t words_mode, void* d_out, uint64_t out_cap, uint64_t* n_out) {
+// What every entry point checks before it does anything, in the order a bad call's status and text
+// depend on.  `device`: out, doc_off and tok_off are device pointers, read there by words.
+int me_check(gbpe_ctx* ctx, const gbpe_bpe* bp, const gbpe_specials* sp, bool special, bool batch, bool device,
+             const void* bytes, uint64_t n, const void* doc_off, uint64_t n_docs, const void* word_starts,
+             uint32_t words_mode, const void* out, uint64_t out_cap, const void* tok_off, uint64_t* n_out) {
     if (special && !sp) {
         if (n_out) *n_out = 0;
         return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe encode (special): no special table");
     }
-    if (!ctx || !bp || !n_out || (n && !d_bytes) || (out_cap && !d_out))
+    if (!ctx || !bp || !n_out || (batch && (!tok_off || (n_docs && !doc_off))) || (n && (!batch || n_docs) && !bytes) ||
+        (out_cap && !out))
         return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
     *n_out = 0;
-    const int rc = me_words_check(ctx, d_word_starts, words_mode);
-    if (rc != GBPE_OK) return rc;
-    if ((uintptr_t)d_out & 3u) return gbpe_set_error(ctx, GBPE_E_INVALID, "d_out must be 4-byte aligned");
-    if (n == 0) return GBPE_OK;
-    return me_run(ctx, bp, sp, "bpe encode (words)", (const uint8_t*)d_bytes, n, (const uint8_t*)d_word_starts, words_mode,
-                  (uint32_t*)d_out, out_cap, nullptr, n_out);
+    const int rc = me_words_check(ctx, word_starts, words_mode);
+    if (rc != GBPE_OK || !device) return rc;
+    if ((uintptr_t)out & 3u) return gbpe_set_error(ctx, GBPE_E_INVALID, "d_out must be 4-byte aligned");
+    if (batch && (((uintptr_t)doc_off | (uintptr_t)tok_off) & 7u))
+        return gbpe_set_error(ctx, GBPE_E_INVALID, "d_doc_off and d_tok_off must be 8-byte aligned");
+    return GBPE_OK;
 }
 
-int me_words_host(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, bool special, const uint8_t* bytes, uint64_t n,
-                  const uint8_t* word_starts, uint32_t words_mode, uint32_t* out, uint64_t out_cap, uint64_t* n_out) {
-    if (special && !sp) {
-        if (n_out) *n_out = 0;
-        return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe encode (special): no special table");
-    }
-    if (!ctx || !bp || !n_out || (n && !bytes) || (out_cap && !out))
-        return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
-    *n_out = 0;
-    int rc = me_words_check(ctx, word_starts, words_mode);
+int me_device(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, bool special, bool batch, const void* d_bytes,
+              uint64_t n, const void* d_doc_off, uint64_t n_docs, const void* d_word_starts, uint32_t words_mode,
+              void* d_out, uint64_t out_cap, void* d_tok_off, uint64_t* n_out) {
+    const int rc = me_check(ctx, bp, sp, special, batch, true, d_bytes, n, d_doc_off, n_docs, d_word_starts, words_mode,
+                            d_out, out_cap, d_tok_off, n_out);
     if (rc != GBPE_OK) return rc;
-    if (n == 0) return GBPE_OK;
-    // one upload of the bytes (and the mask); at most one token per byte comes back
+    if (n == 0 || (batch && n_docs == 0)) {
+        if (batch) {
+            GBPE_HIP(ctx, hipMemsetAsync(d_tok_off, 0, (n_docs + 1) * 8, ctx->stream));
+            GBPE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        return GBPE_OK;
+    }
+    const MeDocJob docs{(const uint64_t*)d_doc_off, n_docs, (uint64_t*)d_tok_off};
+    return me_run(ctx, bp, sp, batch ? "bpe encode batch" : "bpe encode (words)", (const uint8_t*)d_bytes, n, (const uint8_t*)d_word_starts, words_mode,
+                  (uint32_t*)d_out, out_cap, batch ? &docs : nullptr, n_out);
+}
+
+// Host buffers: one upload of the offsets (a batch call), the bytes (and the mask), me_run, and back
+// come the token offsets (a batch call) and the tokens that fit: at most one per byte.
+int me_host(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, bool special, bool batch, const uint8_t* bytes, uint64_t n,
+            const uint64_t* doc_off, uint64_t n_docs, const uint8_t* word_starts, uint32_t words_mode, uint32_t* out,
+            uint64_t out_cap, uint64_t* tok_off, uint64_t* n_out) {
+    int rc = me_check(ctx, bp, sp, special, batch, false, bytes, n, doc_off, n_docs, word_starts, words_mode, out, out_cap,
+                      tok_off, n_out);
+    if (rc != GBPE_OK) return rc;
+    const char* what = batch ? "bpe encode batch" : "bpe encode (words)";
+    if (n == 0 || (batch && n_docs == 0)) {
+        if (batch)
+            for (uint64_t d = 0; d <= n_docs; ++d) tok_off[d] = 0;
+        return GBPE_OK;
+    }
+    if (batch) {
+        rc = gbpe_doc_offsets_check(ctx, what, doc_off, n_docs, n);   // before anything is launched
+        if (rc != GBPE_OK) return rc;
+    }
     const uint64_t cap = out_cap < n ? out_cap : n;
-    const uint64_t o_ws = up16(n), o_out = o_ws + (word_starts ? up16(n) : 0);
+    const uint64_t off_bytes = batch ? 8 * (n_docs + 1) : 0;
+    const uint64_t o_tok = up16(off_bytes), o_in = 2 * o_tok, o_ws = o_in + up16(n);
+    const uint64_t o_out = o_ws + (word_starts ? up16(n) : 0);
     GbpeArray<uint8_t> io;
     GBPE_HIP(ctx, io.reserve(ctx, o_out + 4 * cap + 16));
     hipStream_t s = ctx->stream;
     uint8_t* d_ws = word_starts ? io.p + o_ws : nullptr;
-    hipError_t e = hipMemcpyAsync(io.p, bytes, n, hipMemcpyHostToDevice, s);
+    hipError_t e = batch ? hipMemcpyAsync(io.p, doc_off, off_bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+    if (e == hipSuccess) e = hipMemcpyAsync(io.p + o_in, bytes, n, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && word_starts) e = hipMemcpyAsync(d_ws, word_starts, n, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
-        rc = me_run(ctx, bp, sp, "bpe encode (words)", io.p, n, d_ws, words_mode, (uint32_t*)(io.p + o_out), cap, nullptr,
-                    n_out);
+        const MeDocJob docs{(const uint64_t*)io.p, n_docs, (uint64_t*)(io.p + o_tok)};
+        rc = me_run(ctx, bp, sp, what, io.p + o_in, n, d_ws, words_mode, (uint32_t*)(io.p + o_out), cap,
+                    batch ? &docs : nullptr, n_out);
         if (rc != GBPE_OK && rc != GBPE_E_CAPACITY) return rc;   // (synchronised there)
+        if (batch) e = hipMemcpyAsync(tok_off, io.p + o_tok, off_bytes, hipMemcpyDeviceToHost, s);
         const uint64_t fit = *n_out < cap ? *n_out : cap;
-        if (fit) e = hipMemcpyAsync(out, io.p + o_out, fit * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && fit) e = hipMemcpyAsync(out, io.p + o_out, fit * 4, hipMemcpyDeviceToHost, s);
     }
     const hipError_t es = hipStreamSynchronize(s);
     if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return gbpe_set_error(ctx, GBPE_E_DEVICE, "bpe encode (words) failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return gbpe_set_error(ctx, GBPE_E_DEVICE, "%s failed: %s", what, hipGetErrorString(e));
     return rc;
 }
 
@@ -874,25 +865,28 @@ int me_words_host(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, bool spe
 extern "C" int gbpe_bpe_encode_words_device(gbpe_ctx* ctx, gbpe_bpe* bp, const void* d_bytes, uint64_t n,
                                             const void* d_word_starts, uint32_t words_mode, void* d_out, uint64_t out_cap,
                                             uint64_t* n_out) {
-    return me_words_device(ctx, bp, nullptr, false, d_bytes, n, d_word_starts, words_mode, d_out, out_cap, n_out);
+    return me_device(ctx, bp, nullptr, false, false, d_bytes, n, nullptr, 0, d_word_starts, words_mode, d_out, out_cap,
+                     nullptr, n_out);
 }
 
 extern "C" int gbpe_bpe_encode_special_device(gbpe_ctx* ctx, gbpe_bpe* bp, gbpe_specials* sp, const void* d_bytes, uint64_t n,
                                               const void* d_word_starts, uint32_t words_mode, void* d_out, uint64_t out_cap,
                                               uint64_t* n_out) {
-    return me_words_device(ctx, bp, sp, true, d_bytes, n, d_word_starts, words_mode, d_out, out_cap, n_out);
+    return me_device(ctx, bp, sp, true, false, d_bytes, n, nullptr, 0, d_word_starts, words_mode, d_out, out_cap, nullptr,
+                     n_out);
 }
 
 extern "C" int gbpe_bpe_encode_words(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* bytes, uint64_t n,
                                      const uint8_t* word_starts, uint32_t words_mode, uint32_t* out, uint64_t out_cap,
                                      uint64_t* n_out) {
-    return me_words_host(ctx, bp, nullptr, false, bytes, n, word_starts, words_mode, out, out_cap, n_out);
+    return me_host(ctx, bp, nullptr, false, false, bytes, n, nullptr, 0, word_starts, words_mode, out, out_cap, nullptr,
+                   n_out);
 }
 
 extern "C" int gbpe_bpe_encode_special(gbpe_ctx* ctx, gbpe_bpe* bp, gbpe_specials* sp, const uint8_t* bytes, uint64_t n,
                                        const uint8_t* word_starts, uint32_t words_mode, uint32_t* out, uint64_t out_cap,
                                        uint64_t* n_out) {
-    return me_words_host(ctx, bp, sp, true, bytes, n, word_starts, words_mode, out, out_cap, n_out);
+    return me_host(ctx, bp, sp, true, false, bytes, n, nullptr, 0, word_starts, words_mode, out, out_cap, nullptr, n_out);
 }
 
 // the whole string: no word cuts (the words contract, gpubpe.h)
@@ -901,110 +895,35 @@ extern "C" int gbpe_bpe_encode(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* bytes
     return gbpe_bpe_encode_words(ctx, bp, bytes, n, nullptr, GBPE_WORDS_NONE, out, out_cap, n_out);
 }
 
-// ── many documents in one call (gbpe_bpe_encode_words_batch*) ──
-
-namespace {
-
-int me_batch_device(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, bool special, const void* d_bytes, uint64_t n,
-                    const void* d_doc_off, uint64_t n_docs, const void* d_word_starts, uint32_t words_mode, void* d_out,
-                    uint64_t out_cap, void* d_tok_off, uint64_t* n_out) {
-    if (special && !sp) {
-        if (n_out) *n_out = 0;
-        return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe encode (special): no special table");
-    }
-    if (!ctx || !bp || !n_out || !d_tok_off || (n_docs && !d_doc_off) || (n && n_docs && !d_bytes) || (out_cap && !d_out))
-        return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
-    *n_out = 0;
-    const int rc = me_words_check(ctx, d_word_starts, words_mode);
-    if (rc != GBPE_OK) return rc;
-    if ((uintptr_t)d_out & 3u) return gbpe_set_error(ctx, GBPE_E_INVALID, "d_out must be 4-byte aligned");
-    if (((uintptr_t)d_doc_off | (uintptr_t)d_tok_off) & 7u)
-        return gbpe_set_error(ctx, GBPE_E_INVALID, "d_doc_off and d_tok_off must be 8-byte aligned");
-    if (n == 0 || n_docs == 0) {
-        GBPE_HIP(ctx, hipMemsetAsync(d_tok_off, 0, (n_docs + 1) * 8, ctx->stream));
-        GBPE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return GBPE_OK;
-    }
-    const MeDocJob docs{(const uint64_t*)d_doc_off, n_docs, (uint64_t*)d_tok_off};
-    return me_run(ctx, bp, sp, "bpe encode batch", (const uint8_t*)d_bytes, n, (const uint8_t*)d_word_starts, words_mode,
-                  (uint32_t*)d_out, out_cap, &docs, n_out);
-}
-
-int me_batch_host(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, bool special, const uint8_t* bytes, uint64_t n,
-                  const uint64_t* doc_off, uint64_t n_docs, const uint8_t* word_starts, uint32_t words_mode, uint32_t* out,
-                  uint64_t out_cap, uint64_t* tok_off, uint64_t* n_out) {
-    if (special && !sp) {
-        if (n_out) *n_out = 0;
-        return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe encode (special): no special table");
-    }
-    if (!ctx || !bp || !n_out || !tok_off || (n_docs && !doc_off) || (n && n_docs && !bytes) || (out_cap && !out))
-        return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
-    *n_out = 0;
-    int rc = me_words_check(ctx, word_starts, words_mode);
-    if (rc != GBPE_OK) return rc;
-    if (n == 0 || n_docs == 0) {
-        for (uint64_t d = 0; d <= n_docs; ++d) tok_off[d] = 0;
-        return GBPE_OK;
-    }
-    rc = gbpe_doc_offsets_check(ctx, "bpe encode batch", doc_off, n_docs, n);   // before anything is launched
-    if (rc != GBPE_OK) return rc;
-    // one upload of the offsets, the bytes (and the mask); at most one token per byte comes back
-    const uint64_t cap = out_cap < n ? out_cap : n;
-    const uint64_t o_tok = up16(8 * (n_docs + 1)), o_in = 2 * o_tok, o_ws = o_in + up16(n);
-    const uint64_t o_out = o_ws + (word_starts ? up16(n) : 0);
-    GbpeArray<uint8_t> io;
-    GBPE_HIP(ctx, io.reserve(ctx, o_out + 4 * cap + 16));
-    hipStream_t s = ctx->stream;
-    uint8_t* d_ws = word_starts ? io.p + o_ws : nullptr;
-    hipError_t e = hipMemcpyAsync(io.p, doc_off, 8 * (n_docs + 1), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(io.p + o_in, bytes, n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && word_starts) e = hipMemcpyAsync(d_ws, word_starts, n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        const MeDocJob docs{(const uint64_t*)io.p, n_docs, (uint64_t*)(io.p + o_tok)};
-        rc = me_run(ctx, bp, sp, "bpe encode batch", io.p + o_in, n, d_ws, words_mode, (uint32_t*)(io.p + o_out), cap,
-                    &docs, n_out);
-        if (rc != GBPE_OK && rc != GBPE_E_CAPACITY) return rc;   // (synchronised there)
-        e = hipMemcpyAsync(tok_off, io.p + o_tok, 8 * (n_docs + 1), hipMemcpyDeviceToHost, s);
-        const uint64_t fit = *n_out < cap ? *n_out : cap;
-        if (e == hipSuccess && fit) e = hipMemcpyAsync(out, io.p + o_out, fit * 4, hipMemcpyDeviceToHost, s);
-    }
-    const hipError_t es = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return gbpe_set_error(ctx, GBPE_E_DEVICE, "bpe encode batch failed: %s", hipGetErrorString(e));
-    return rc;
-}
-
-}  // namespace
-
 extern "C" int gbpe_bpe_encode_words_batch_device(gbpe_ctx* ctx, gbpe_bpe* bp, const void* d_bytes, uint64_t n,
                                                   const void* d_doc_off, uint64_t n_docs, const void* d_word_starts,
                                                   uint32_t words_mode, void* d_out, uint64_t out_cap, void* d_tok_off,
                                                   uint64_t* n_out) {
-    return me_batch_device(ctx, bp, nullptr, false, d_bytes, n, d_doc_off, n_docs, d_word_starts, words_mode, d_out, out_cap,
-                           d_tok_off, n_out);
+    return me_device(ctx, bp, nullptr, false, true, d_bytes, n, d_doc_off, n_docs, d_word_starts, words_mode, d_out, out_cap,
+                     d_tok_off, n_out);
 }
 
 extern "C" int gbpe_bpe_encode_special_batch_device(gbpe_ctx* ctx, gbpe_bpe* bp, gbpe_specials* sp, const void* d_bytes,
                                                     uint64_t n, const void* d_doc_off, uint64_t n_docs,
                                                     const void* d_word_starts, uint32_t words_mode, void* d_out,
                                                     uint64_t out_cap, void* d_tok_off, uint64_t* n_out) {
-    return me_batch_device(ctx, bp, sp, true, d_bytes, n, d_doc_off, n_docs, d_word_starts, words_mode, d_out, out_cap,
-                           d_tok_off, n_out);
+    return me_device(ctx, bp, sp, true, true, d_bytes, n, d_doc_off, n_docs, d_word_starts, words_mode, d_out, out_cap,
+                     d_tok_off, n_out);
 }
 
 extern "C" int gbpe_bpe_encode_words_batch(gbpe_ctx* ctx, gbpe_bpe* bp, const uint8_t* bytes, uint64_t n,
                                            const uint64_t* doc_off, uint64_t n_docs, const uint8_t* word_starts,
                                            uint32_t words_mode, uint32_t* out, uint64_t out_cap, uint64_t* tok_off,
                                            uint64_t* n_out) {
-    return me_batch_host(ctx, bp, nullptr, false, bytes, n, doc_off, n_docs, word_starts, words_mode, out, out_cap, tok_off,
-                         n_out);
+    return me_host(ctx, bp, nullptr, false, true, bytes, n, doc_off, n_docs, word_starts, words_mode, out, out_cap, tok_off,
+                   n_out);
 }
 
 extern "C" int gbpe_bpe_encode_special_batch(gbpe_ctx* ctx, gbpe_bpe* bp, gbpe_specials* sp, const uint8_t* bytes, uint64_t n,
                                              const uint64_t* doc_off, uint64_t n_docs, const uint8_t* word_starts,
                                              uint32_t words_mode, uint32_t* out, uint64_t out_cap, uint64_t* tok_off,
                                              uint64_t* n_out) {
-    return me_batch_host(ctx, bp, sp, true, bytes, n, doc_off, n_docs, word_starts, words_mode, out, out_cap, tok_off, n_out);
+    return me_host(ctx, bp, sp, true, true, bytes, n, doc_off, n_docs, word_starts, words_mode, out, out_cap, tok_off, n_out);
 }
 
 extern "C" int gbpe_bpe_encode_last_timing(gbpe_ctx* ctx, double* ms_starts, double* ms_walk, double* ms_compact) {
