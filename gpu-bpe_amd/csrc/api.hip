@@ -59,6 +59,9 @@ static const char* const kKernelNames[] = {
     "k_me_walk_special",      // k_me_walk_docs<CS, true>: a special's span is one token
     // ids above 0xFFFF (gbpe_bpe_upload_wide)
     "k_me_walk_wide",         // k_me_walk / k_me_walk_docs<..., WIDE = true>: every walk above on {a, b, rank, new id} slots
+    // cl100k_base word starts (gbpe_pretokenize_cl100k*, GBPE_WORDS_CL100K)
+    "k_pretok_cl100k",        // k_ptc_scan1 / k_ptc_scan2 / k_ptc_mark: the split pattern's rules + its three scans
+    "k_pretok_cl100k_docs",   // k_ptc_scan1<true> / k_ptc_mark<true>: the same bounded by the document flags
 };
 
 // ── context memory pool (common.h GbpePool) ───────────────────────────────

@@ -194,6 +194,8 @@ inline std::string gbpe_debug_unknown() {
 int gbpe_pretok_gpt4_launch(gbpe_ctx* ctx, const uint8_t* d_bytes, uint64_t n, uint8_t* d_ws);
 // the same for many documents in one buffer: d_flags[n] (4-byte aligned) is non-zero where a document starts
 int gbpe_pretok_gpt4_docs_launch(gbpe_ctx* ctx, const uint8_t* d_bytes, uint64_t n, const uint8_t* d_flags, uint8_t* d_ws);
+// cl100k_base word starts of the same, d_flags == nullptr: one text
+int gbpe_pretok_cl100k_launch(gbpe_ctx* ctx, const uint8_t* d_bytes, uint64_t n, const uint8_t* d_flags, uint8_t* d_ws);
 // Document offsets of the batch calls (doc_off[n_docs + 1], from 0 to n, non-decreasing).
 // k_doc_flags (pretok.hip), one lane per document: ORs what is wrong into *d_invalid
 // (nullptr: unchecked) and `bit` into d_flags[doc_off[d]] (nullptr: no flags) for doc_off[d] < n.

@@ -627,10 +627,13 @@ struct MeDocJob {   // the documents of a batch call, n_docs > 0
 // the mode's mask of every document — of every piece between accepted specials — alone (mode NONE:
 // nothing) | the starts of the documents, of the specials and of the pieces after them;
 // ME_DOC_BIT = a document starts here; ME_SP_BIT / ME_SPIN_BIT = a special's first / other bytes.
-// The GPT-4 rules see a piece alone through the document form of the pre-tokeniser: w.flags holds
+// The GPT-4 and cl100k rules see a piece alone through the document form of the pre-tokeniser: w.flags holds
 // the document starts, then (k_sp_accept) the pieces' too.  The other modes' masks look one byte
 // back at most, so forcing a piece's first byte is all they need.  The first kernel checks the
 // offsets into the second word of w.back (zeroed by the caller).
+// the modes whose mask comes from a pre-tokeniser's kernels (pretok.hip)
+bool me_pretok(uint32_t mode) { return mode == GBPE_WORDS_GPT4 || mode == GBPE_WORDS_CL100K; }
+
 int me_mask(gbpe_ctx* ctx, const uint8_t* d_in, uint64_t n, const uint8_t* d_ws, uint32_t mode, const MeDocJob* docs,
             const gbpe_specials* sp, const MeWork& w) {
     hipStream_t s = ctx->stream;
@@ -640,10 +643,12 @@ int me_mask(gbpe_ctx* ctx, const uint8_t* d_in, uint64_t n, const uint8_t* d_ws,
     if (docs) rc = gbpe_doc_flags_launch(ctx, docs->d_doc_off, docs->n_docs, n, w.flags, w.flags ? 1u : 0u, d_invalid);
     if (rc == GBPE_OK && sp)
         rc = gbpe_specials_launch(ctx, sp, d_in, n, docs ? w.flags : nullptr, w.cand, w.mark,
-                                  mode == GBPE_WORDS_GPT4 ? w.flags : nullptr);
+                                  me_pretok(mode) ? w.flags : nullptr);
     if (rc != GBPE_OK) return rc;
     if (mode == GBPE_WORDS_GPT4) {
         rc = gbpe_pretok_gpt4_docs_launch(ctx, d_in, n, w.flags, w.mask);
+    } else if (mode == GBPE_WORDS_CL100K) {
+        rc = gbpe_pretok_cl100k_launch(ctx, d_in, n, w.flags, w.mask);
     } else if (mode == GBPE_WORDS_NONE) {
         GBPE_HIP(ctx, hipMemsetAsync(w.mask, 0, n, s));
     } else if (mode == GBPE_WORDS_MASK) {
@@ -677,9 +682,9 @@ int me_run(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, const char* wha
     const uint64_t nblk = gbpe_div_up(nchunks, SCAN_BLK);
     GbpeArray<uint8_t> work, mask, arena;
     MeWork w;
-    // (flags: the GPT-4 rules' piece starts; the document starts the matcher must not cross)
+    // (flags: the pre-tokenisers' piece starts; the document starts the matcher must not cross)
     GBPE_HIP(ctx, me_layout(ctx, work, n, cs, nchunks, nblk, docs ? docs->n_docs : 0,
-                            (docs || sp) && (mode == GBPE_WORDS_GPT4 || (docs && sp)), sp != nullptr, &w));
+                            (docs || sp) && (me_pretok(mode) || (docs && sp)), sp != nullptr, &w));
     const MeTable t{bp->slots, bp->mask, bp->cross};
     const uint64_t cell = docs ? 16 : 8;   // of w.back: a batch call also reads the offsets' verdict
 
@@ -689,10 +694,11 @@ int me_run(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, const char* wha
         GBPE_HIP(ctx, hipMemsetAsync(w.back, 0, cell, s));
         rc = me_mask(ctx, d_in, n, d_ws, mode, docs, sp, w);
         d_ws = w.mask;
-    } else if (mode == GBPE_WORDS_HEURISTIC || mode == GBPE_WORDS_GPT4) {
+    } else if (mode == GBPE_WORDS_HEURISTIC || me_pretok(mode)) {
         GBPE_HIP(ctx, mask.reserve(ctx, n));
-        rc = mode == GBPE_WORDS_GPT4 ? gbpe_pretok_gpt4_launch(ctx, d_in, n, mask.p)
-                                     : gbpe_word_boundary_launch(ctx, d_in, n, mask.p);
+        rc = mode == GBPE_WORDS_GPT4     ? gbpe_pretok_gpt4_launch(ctx, d_in, n, mask.p)
+             : mode == GBPE_WORDS_CL100K ? gbpe_pretok_cl100k_launch(ctx, d_in, n, nullptr, mask.p)
+                                         : gbpe_word_boundary_launch(ctx, d_in, n, mask.p);
         d_ws = mask.p;
     }
     if (rc != GBPE_OK) {
@@ -765,7 +771,7 @@ int me_run(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, const char* wha
 }
 
 int me_words_check(gbpe_ctx* ctx, const void* word_starts, uint32_t mode) {
-    if (mode > GBPE_WORDS_GPT4) return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe encode: unknown words mode %u", mode);
+    if (mode > GBPE_WORDS_CL100K) return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe encode: unknown words mode %u", mode);
     if ((word_starts != nullptr) != (mode == GBPE_WORDS_MASK))
         return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe encode: word_starts goes with GBPE_WORDS_MASK, and only with it");
     return GBPE_OK;

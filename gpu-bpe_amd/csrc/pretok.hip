@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "unicode_classes.h"
+#include "unicode_classes_cl100k.h"
 
 namespace {
 
@@ -537,22 +538,31 @@ __global__ __launch_bounds__(256) void k_doc_flags(const uint64_t* __restrict__ 
     if (flags && a < n) flags[a] = (uint8_t)(flags[a] | v);
 }
 
+#include "pretok_cl100k.h"
+
+enum PtRules { PT_GPT4 = 0, PT_CL100K = 1 };
+
 struct UniTables {
     uint16_t* idx = nullptr;
     uint8_t* cls = nullptr;
     int device = -1;
 };
 
-int uni_tables(gbpe_ctx* ctx, const uint16_t** idx, const uint8_t** cls) {
-    static UniTables tabs[64];
+// the rules' class table on the context's device, uploaded on first use
+int uni_tables(gbpe_ctx* ctx, PtRules rules, const uint16_t** idx, const uint8_t** cls) {
+    static UniTables tabs[2][64];
     const int d = ctx->device;
     if (d < 0 || d >= 64) return gbpe_set_error(ctx, GBPE_E_INVALID, "device ordinal out of range");
-    UniTables& t = tabs[d];
+    UniTables& t = tabs[rules][d];
     if (!t.idx) {
-        GBPE_HIP(ctx, dev_malloc(ctx, &t.idx, sizeof(kUniIndex)));
-        GBPE_HIP(ctx, dev_malloc(ctx, &t.cls, sizeof(kUniClass)));
-        GBPE_HIP(ctx, hipMemcpy(t.idx, kUniIndex, sizeof(kUniIndex), hipMemcpyHostToDevice));
-        GBPE_HIP(ctx, hipMemcpy(t.cls, kUniClass, sizeof(kUniClass), hipMemcpyHostToDevice));
+        const bool cl = rules == PT_CL100K;
+        const void* hi = cl ? (const void*)kCl100kIndex : (const void*)kUniIndex;
+        const void* hc = cl ? (const void*)kCl100kClass : (const void*)kUniClass;
+        const size_t ni = cl ? sizeof(kCl100kIndex) : sizeof(kUniIndex), nc = cl ? sizeof(kCl100kClass) : sizeof(kUniClass);
+        GBPE_HIP(ctx, dev_malloc(ctx, &t.idx, ni));
+        GBPE_HIP(ctx, dev_malloc(ctx, &t.cls, nc));
+        GBPE_HIP(ctx, hipMemcpy(t.idx, hi, ni, hipMemcpyHostToDevice));
+        GBPE_HIP(ctx, hipMemcpy(t.cls, hc, nc, hipMemcpyHostToDevice));
     }
     *idx = t.idx;
     *cls = t.cls;
@@ -561,17 +571,30 @@ int uni_tables(gbpe_ctx* ctx, const uint16_t** idx, const uint8_t** cls) {
 
 // device-resident form: d_bytes[n] → d_ws[n] (1 = word start), on the context's stream;
 // d_flags (n bytes, 4-byte aligned, non-zero = a document starts here) selects the document form
-int pretok_launch(gbpe_ctx* ctx, const uint8_t* d_bytes, uint64_t n, const uint8_t* d_flags, uint8_t* d_ws) {
+int pretok_launch(gbpe_ctx* ctx, PtRules rules, const uint8_t* d_bytes, uint64_t n, const uint8_t* d_flags,
+                  uint8_t* d_ws) {
     if (n == 0) return GBPE_OK;
     const uint16_t* idx;
     const uint8_t* cls;
-    int rc = uni_tables(ctx, &idx, &cls);
+    int rc = uni_tables(ctx, rules, &idx, &cls);
     if (rc != GBPE_OK) return rc;
     hipStream_t s = ctx->stream;
     const uint64_t nblk = gbpe_div_up(n, PT_BLK);
-    GBPE_HIP(ctx, ctx->pt_agg.reserve(ctx, (nblk + 1) * sizeof(uint32_t)));
+    GBPE_HIP(ctx, ctx->pt_agg.reserve(ctx, (rules == PT_CL100K ? 2 : 1) * (nblk + 1) * sizeof(uint32_t)));
     uint32_t* agg = (uint32_t*)ctx->pt_agg.p;
-    if (d_flags) {
+    if (rules == PT_CL100K) {
+        uint32_t* bagg = agg + nblk + 1;   // the backward aggregates
+        const dim3 g((uint32_t)nblk), b(PT_TPB);
+        if (d_flags) hipLaunchKernelGGL(k_ptc_scan1<true>, g, b, 0, s, d_bytes, n, d_flags, idx, cls, agg, bagg);
+        else hipLaunchKernelGGL(k_ptc_scan1<false>, g, b, 0, s, d_bytes, n, d_flags, idx, cls, agg, bagg);
+        hipLaunchKernelGGL(k_ptc_scan2, dim3(1), dim3(1024), 0, s, agg, bagg, nblk);
+        if (d_flags)
+            hipLaunchKernelGGL(k_ptc_mark<true>, g, b, 0, s, d_bytes, n, d_flags, idx, cls, (const uint32_t*)agg,
+                               (const uint32_t*)bagg, d_ws);
+        else
+            hipLaunchKernelGGL(k_ptc_mark<false>, g, b, 0, s, d_bytes, n, d_flags, idx, cls, (const uint32_t*)agg,
+                               (const uint32_t*)bagg, d_ws);
+    } else if (d_flags) {
         hipLaunchKernelGGL(k_pt_scan1_docs, dim3((uint32_t)nblk), dim3(PT_TPB), 0, s, d_bytes, n, d_flags, idx, cls, agg);
         hipLaunchKernelGGL(k_pt_scan2, dim3(1), dim3(1024), 0, s, agg, nblk);
         hipLaunchKernelGGL(k_pt_mark_docs, dim3((uint32_t)nblk), dim3(PT_TPB), 0, s, d_bytes, n, d_flags, idx, cls,
@@ -589,12 +612,16 @@ int pretok_launch(gbpe_ctx* ctx, const uint8_t* d_bytes, uint64_t n, const uint8
 }  // namespace
 
 int gbpe_pretok_gpt4_launch(gbpe_ctx* ctx, const uint8_t* d_bytes, uint64_t n, uint8_t* d_ws) {
-    return pretok_launch(ctx, d_bytes, n, nullptr, d_ws);
+    return pretok_launch(ctx, PT_GPT4, d_bytes, n, nullptr, d_ws);
 }
 
 int gbpe_pretok_gpt4_docs_launch(gbpe_ctx* ctx, const uint8_t* d_bytes, uint64_t n, const uint8_t* d_flags,
                                  uint8_t* d_ws) {
-    return pretok_launch(ctx, d_bytes, n, d_flags, d_ws);
+    return pretok_launch(ctx, PT_GPT4, d_bytes, n, d_flags, d_ws);
+}
+
+int gbpe_pretok_cl100k_launch(gbpe_ctx* ctx, const uint8_t* d_bytes, uint64_t n, const uint8_t* d_flags, uint8_t* d_ws) {
+    return pretok_launch(ctx, PT_CL100K, d_bytes, n, d_flags, d_ws);
 }
 
 int gbpe_doc_flags_launch(gbpe_ctx* ctx, const uint64_t* d_doc_off, uint64_t n_docs, uint64_t n, uint8_t* d_flags,
@@ -621,19 +648,23 @@ int gbpe_doc_offsets_error(gbpe_ctx* ctx, const char* what, uint32_t bad) {
                                                        : "do not end at the byte count");
 }
 
-extern "C" int gbpe_pretokenize_gpt4_device(gbpe_ctx* ctx, const void* d_bytes, uint64_t n, void* d_ws) {
+// ── the entry points, each for both sets of rules ──────────────────────────
+
+namespace {
+
+int pretok_device(gbpe_ctx* ctx, PtRules rules, const void* d_bytes, uint64_t n, void* d_ws) {
     if (!ctx || (n && (!d_bytes || !d_ws))) return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
-    return gbpe_pretok_gpt4_launch(ctx, (const uint8_t*)d_bytes, n, (uint8_t*)d_ws);
+    return pretok_launch(ctx, rules, (const uint8_t*)d_bytes, n, nullptr, (uint8_t*)d_ws);
 }
 
-extern "C" int gbpe_pretokenize_gpt4(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, uint8_t* ws_out) {
+int pretok_host(gbpe_ctx* ctx, PtRules rules, const uint8_t* bytes, uint64_t n, uint8_t* ws_out) {
     if (!ctx || (n && (!bytes || !ws_out))) return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
     if (n == 0) return GBPE_OK;
     hipStream_t s = ctx->stream;
     GbpeArray<uint8_t> io;   // one pooled block: bytes, mask
     GBPE_HIP(ctx, io.reserve(ctx, 2 * n));
     hipError_t e = hipMemcpyAsync(io.p, bytes, n, hipMemcpyHostToDevice, s);
-    const int rc = e == hipSuccess ? gbpe_pretok_gpt4_launch(ctx, io.p, n, io.p + n) : GBPE_OK;
+    const int rc = e == hipSuccess ? pretok_launch(ctx, rules, io.p, n, nullptr, io.p + n) : GBPE_OK;
     if (e == hipSuccess && rc == GBPE_OK) e = hipMemcpyAsync(ws_out, io.p + n, n, hipMemcpyDeviceToHost, s);
     const hipError_t es = hipStreamSynchronize(s);   // (always: the block goes back to the pool on return)
     if (e == hipSuccess) e = es;
@@ -644,11 +675,9 @@ extern "C" int gbpe_pretokenize_gpt4(gbpe_ctx* ctx, const uint8_t* bytes, uint64
 
 // ── many documents in one buffer ──────────────────────────────
 
-namespace {
-
 // flags + mask of checked inputs; d_work: n flag bytes, then (16-byte aligned) the bad-offsets word.
 // The offsets are checked by the first kernel and read back before any other kernel runs.
-int pretok_batch_run(gbpe_ctx* ctx, const uint8_t* d_bytes, uint64_t n, const uint64_t* d_doc_off, uint64_t n_docs,
+int pretok_batch_run(gbpe_ctx* ctx, PtRules rules, const uint8_t* d_bytes, uint64_t n, const uint64_t* d_doc_off, uint64_t n_docs,
                      uint8_t* d_work, uint8_t* d_ws) {
     hipStream_t s = ctx->stream;
     uint32_t* d_invalid = (uint32_t*)(d_work + ((n + 15) & ~15ull));
@@ -660,20 +689,18 @@ int pretok_batch_run(gbpe_ctx* ctx, const uint8_t* d_bytes, uint64_t n, const ui
     uint32_t bad = 0;
     memcpy(&bad, ctx->enc_host_total, 4);
     if (bad) return gbpe_doc_offsets_error(ctx, "pretokenize batch", bad);   // nothing else was launched
-    return gbpe_pretok_gpt4_docs_launch(ctx, d_bytes, n, d_work, d_ws);
+    return pretok_launch(ctx, rules, d_bytes, n, d_work, d_ws);
 }
 
-}  // namespace
-
-extern "C" int gbpe_pretokenize_gpt4_batch_device(gbpe_ctx* ctx, const void* d_bytes, uint64_t n, const void* d_doc_off,
-                                                  uint64_t n_docs, void* d_ws) {
+int pretok_batch_device(gbpe_ctx* ctx, PtRules rules, const void* d_bytes, uint64_t n, const void* d_doc_off,
+                        uint64_t n_docs, void* d_ws) {
     if (!ctx || (n_docs && !d_doc_off) || (n && n_docs && (!d_bytes || !d_ws)))
         return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
     if ((uintptr_t)d_doc_off & 7u) return gbpe_set_error(ctx, GBPE_E_INVALID, "d_doc_off must be 8-byte aligned");
     if (n == 0 || n_docs == 0) return GBPE_OK;
     GbpeArray<uint8_t> work;
     GBPE_HIP(ctx, work.reserve(ctx, n + 48));
-    const int rc = pretok_batch_run(ctx, (const uint8_t*)d_bytes, n, (const uint64_t*)d_doc_off, n_docs, work.p,
+    const int rc = pretok_batch_run(ctx, rules, (const uint8_t*)d_bytes, n, (const uint64_t*)d_doc_off, n_docs, work.p,
                                     (uint8_t*)d_ws);
     const hipError_t e = hipStreamSynchronize(ctx->stream);   // (the flags go back to the pool on return)
     if (rc != GBPE_OK) return rc;
@@ -681,8 +708,8 @@ extern "C" int gbpe_pretokenize_gpt4_batch_device(gbpe_ctx* ctx, const void* d_b
     return GBPE_OK;
 }
 
-extern "C" int gbpe_pretokenize_gpt4_batch(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, const uint64_t* doc_off,
-                                           uint64_t n_docs, uint8_t* ws_out) {
+int pretok_batch_host(gbpe_ctx* ctx, PtRules rules, const uint8_t* bytes, uint64_t n, const uint64_t* doc_off,
+                      uint64_t n_docs, uint8_t* ws_out) {
     if (!ctx || (n_docs && !doc_off) || (n && n_docs && (!bytes || !ws_out)))
         return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
     if (n == 0 || n_docs == 0) return GBPE_OK;
@@ -696,7 +723,7 @@ extern "C" int gbpe_pretokenize_gpt4_batch(gbpe_ctx* ctx, const uint8_t* bytes, 
     GBPE_HIP(ctx, io.reserve(ctx, o_work + n + 48));
     hipError_t e = hipMemcpyAsync(io.p, doc_off, 8 * (n_docs + 1), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(io.p + o_in, bytes, n, hipMemcpyHostToDevice, s);
-    rc = e == hipSuccess ? pretok_batch_run(ctx, io.p + o_in, n, (const uint64_t*)io.p, n_docs, io.p + o_work, io.p + o_ws)
+    rc = e == hipSuccess ? pretok_batch_run(ctx, rules, io.p + o_in, n, (const uint64_t*)io.p, n_docs, io.p + o_work, io.p + o_ws)
                          : GBPE_OK;
     if (e == hipSuccess && rc == GBPE_OK) e = hipMemcpyAsync(ws_out, io.p + o_ws, n, hipMemcpyDeviceToHost, s);
     const hipError_t es = hipStreamSynchronize(s);
@@ -706,3 +733,34 @@ extern "C" int gbpe_pretokenize_gpt4_batch(gbpe_ctx* ctx, const uint8_t* bytes, 
     return GBPE_OK;
 }
 
+}  // namespace
+
+extern "C" int gbpe_pretokenize_gpt4_device(gbpe_ctx* ctx, const void* d_bytes, uint64_t n, void* d_ws) {
+    return pretok_device(ctx, PT_GPT4, d_bytes, n, d_ws);
+}
+extern "C" int gbpe_pretokenize_gpt4(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, uint8_t* ws_out) {
+    return pretok_host(ctx, PT_GPT4, bytes, n, ws_out);
+}
+extern "C" int gbpe_pretokenize_gpt4_batch_device(gbpe_ctx* ctx, const void* d_bytes, uint64_t n, const void* d_doc_off,
+                                                  uint64_t n_docs, void* d_ws) {
+    return pretok_batch_device(ctx, PT_GPT4, d_bytes, n, d_doc_off, n_docs, d_ws);
+}
+extern "C" int gbpe_pretokenize_gpt4_batch(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, const uint64_t* doc_off,
+                                           uint64_t n_docs, uint8_t* ws_out) {
+    return pretok_batch_host(ctx, PT_GPT4, bytes, n, doc_off, n_docs, ws_out);
+}
+
+extern "C" int gbpe_pretokenize_cl100k_device(gbpe_ctx* ctx, const void* d_bytes, uint64_t n, void* d_ws) {
+    return pretok_device(ctx, PT_CL100K, d_bytes, n, d_ws);
+}
+extern "C" int gbpe_pretokenize_cl100k(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, uint8_t* ws_out) {
+    return pretok_host(ctx, PT_CL100K, bytes, n, ws_out);
+}
+extern "C" int gbpe_pretokenize_cl100k_batch_device(gbpe_ctx* ctx, const void* d_bytes, uint64_t n, const void* d_doc_off,
+                                                    uint64_t n_docs, void* d_ws) {
+    return pretok_batch_device(ctx, PT_CL100K, d_bytes, n, d_doc_off, n_docs, d_ws);
+}
+extern "C" int gbpe_pretokenize_cl100k_batch(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, const uint64_t* doc_off,
+                                             uint64_t n_docs, uint8_t* ws_out) {
+    return pretok_batch_host(ctx, PT_CL100K, bytes, n, doc_off, n_docs, ws_out);
+}

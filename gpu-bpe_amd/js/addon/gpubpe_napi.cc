@@ -21,6 +21,7 @@
 //   specialsUpload(ctx, bytes, offsets: Float64Array, ids: Uint32Array) -> external; specialsMark(ctx, specials, bytes, offsets | null) -> Uint8Array
 //   bpeEncodeSpecial(ctx, bpe, specials, bytes, wordStarts | null, mode) / bpeEncodeSpecialBatch(ctx, bpe, specials, bytes, offsets, wordStarts | null, mode)
 //   pretokenizeGpt4Batch(ctx, bytes, offsets: Float64Array) -> Uint8Array
+//   pretokenizeCl100k(ctx, bytes) / pretokenizeCl100kBatch(ctx, bytes, offsets) -> Uint8Array: the cl100k_base split
 //   vocabUpload(ctx, bytes: Uint8Array, offsets: Float64Array) -> vocab   vocabFree(vocab)
 //   decode(ctx, vocab, tokens: Uint32Array) -> Promise<Uint8Array>
 //   decodeBatch(ctx, vocab, tokens: Uint32Array, offsets: Float64Array) -> Promise<{bytes: Uint8Array, offsets: Float64Array}>
@@ -287,8 +288,10 @@ napi_value WordBoundary(napi_env env, napi_callback_info info) {
     return ta;
 }
 
-// GPT-4 rule word starts (PreTokenizer.preTokenizeBytes, pre_tokenizer.mjs:459-509)
-napi_value PretokenizeGpt4(napi_env env, napi_callback_info info) {
+// GPT-4 rule word starts (PreTokenizer.preTokenizeBytes, pre_tokenizer.mjs:459-509), or with
+// `cl100k` those of the cl100k_base split pattern (gbpe_pretokenize_cl100k)
+static napi_value pretokenize(napi_env env, napi_callback_info info, bool cl100k) {
+    const char* name = cl100k ? "pretokenizeCl100k" : "pretokenizeGpt4";
     size_t argc = 2;
     napi_value argv[2];
     NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
@@ -296,19 +299,21 @@ napi_value PretokenizeGpt4(napi_env env, napi_callback_info info) {
     const uint8_t* data = nullptr;
     size_t len = 0;
     if (!ctx_usable(c) || argc < 2 || !get_bytes(env, argv[1], &data, &len)) {
-        napi_throw_type_error(env, nullptr, "pretokenizeGpt4(ctx, Uint8Array)");
+        napi_throw_type_error(env, nullptr, cl100k ? "pretokenizeCl100k(ctx, Uint8Array)" : "pretokenizeGpt4(ctx, Uint8Array)");
         return nullptr;
     }
     napi_value ab, ta;
     void* dst = nullptr;
     NAPI_CALL(env, napi_create_arraybuffer(env, len, &dst, &ab));
     std::unique_lock<std::mutex> g(c->mu);
-    int rc = gbpe_pretokenize_gpt4(c->ctx, data, len, static_cast<uint8_t*>(dst));
+    int rc = (cl100k ? gbpe_pretokenize_cl100k : gbpe_pretokenize_gpt4)(c->ctx, data, len, static_cast<uint8_t*>(dst));
     g.unlock();
-    if (rc != GBPE_OK) return throw_status(env, c->ctx, "pretokenizeGpt4", rc);
+    if (rc != GBPE_OK) return throw_status(env, c->ctx, name, rc);
     NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, len, ab, 0, &ta));
     return ta;
 }
+napi_value PretokenizeGpt4(napi_env env, napi_callback_info info) { return pretokenize(env, info, false); }
+napi_value PretokenizeCl100k(napi_env env, napi_callback_info info) { return pretokenize(env, info, true); }
 
 // ── trainer ──────────────────────────────────────────────────────────────
 
@@ -585,7 +590,7 @@ napi_value BpeEncode(napi_env env, napi_callback_info info) {
 }
 
 // bpeEncodeWords(ctx, bpe, bytes, wordStarts | null, mode): the merges inside each
-// word alone (gbpe_bpe_encode_words; mode = GBPE_WORDS_*: 1 takes the mask, 2 and 3
+// word alone (gbpe_bpe_encode_words; mode = GBPE_WORDS_*: 1 takes the mask, 2, 3 and 4
 // compute it on the device)
 // (`special`: bpeEncodeSpecial, the same with a special table after bpe — gbpe_bpe_encode_special)
 napi_value bpe_encode_words(napi_env env, napi_callback_info info, bool special) {
@@ -790,8 +795,9 @@ napi_value SpecialsMark(napi_env env, napi_callback_info info) {
 }
 
 // pretokenizeGpt4Batch(ctx, bytes, offsets) -> Uint8Array: each document's own GPT-4 word starts
-// (gbpe_pretokenize_gpt4_batch)
-napi_value PretokenizeGpt4Batch(napi_env env, napi_callback_info info) {
+// (gbpe_pretokenize_gpt4_batch); pretokenizeCl100kBatch: its own cl100k_base ones (gbpe_pretokenize_cl100k_batch)
+static napi_value pretokenize_batch(napi_env env, napi_callback_info info, bool cl100k) {
+    const char* name = cl100k ? "pretokenizeCl100kBatch" : "pretokenizeGpt4Batch";
     size_t argc = 3;
     napi_value argv[3];
     NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
@@ -801,19 +807,23 @@ napi_value PretokenizeGpt4Batch(napi_env env, napi_callback_info info) {
     std::vector<uint64_t> doc_off;
     if (!ctx_usable(c) || argc < 3 || !get_bytes(env, argv[1], &data, &len) || !get_doc_offsets(env, argv[2], &doc_off)) {
         napi_throw_type_error(env, nullptr,
-                              "pretokenizeGpt4Batch(ctx, Uint8Array, offsets: Float64Array of non-negative integers)");
+                              cl100k ? "pretokenizeCl100kBatch(ctx, Uint8Array, offsets: Float64Array of non-negative integers)"
+                                     : "pretokenizeGpt4Batch(ctx, Uint8Array, offsets: Float64Array of non-negative integers)");
         return nullptr;
     }
     napi_value ab, ta;
     void* dst = nullptr;
     NAPI_CALL(env, napi_create_arraybuffer(env, len, &dst, &ab));
     std::unique_lock<std::mutex> g(c->mu);
-    int rc = gbpe_pretokenize_gpt4_batch(c->ctx, data, len, doc_off.data(), doc_off.size() - 1, static_cast<uint8_t*>(dst));
+    int rc = (cl100k ? gbpe_pretokenize_cl100k_batch : gbpe_pretokenize_gpt4_batch)(
+        c->ctx, data, len, doc_off.data(), doc_off.size() - 1, static_cast<uint8_t*>(dst));
     g.unlock();
-    if (rc != GBPE_OK) return throw_status(env, c->ctx, "pretokenizeGpt4Batch", rc);
+    if (rc != GBPE_OK) return throw_status(env, c->ctx, name, rc);
     NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, len, ab, 0, &ta));
     return ta;
 }
+napi_value PretokenizeGpt4Batch(napi_env env, napi_callback_info info) { return pretokenize_batch(env, info, false); }
+napi_value PretokenizeCl100kBatch(napi_env env, napi_callback_info info) { return pretokenize_batch(env, info, true); }
 
 struct EncodeWork {
     napi_async_work work = nullptr;
@@ -1216,6 +1226,8 @@ napi_value Init(napi_env env, napi_value exports) {
         {"bpeEncodeSpecial", nullptr, BpeEncodeSpecial, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"bpeEncodeSpecialBatch", nullptr, BpeEncodeSpecialBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"pretokenizeGpt4Batch", nullptr, PretokenizeGpt4Batch, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"pretokenizeCl100k", nullptr, PretokenizeCl100k, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"pretokenizeCl100kBatch", nullptr, PretokenizeCl100kBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"vocabUpload", nullptr, VocabUpload, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"vocabFree", nullptr, VocabFree, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"decode", nullptr, Decode, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -4,8 +4,9 @@
  * with word starts, inside each word alone (pre-tokenise, then BPE per word).
  * encode(text) → { tokens, text, vocab, vocabStrings } as the reference's
  * (model = { vocab, vocabStrings, merges }).  opts = { wordStarts: Uint8Array (one
- * entry per byte, non-zero = word start) } or { words: 'gpt4' | 'heuristic' } (the
- * mask computed on the device); without opts no word is cut.  encodeBatch(docs,
+ * entry per byte, non-zero = word start) } or { words: 'gpt4' | 'heuristic' | 'cl100k' }
+ * (the mask computed on the device; 'cl100k' is the exact cl100k_base split pattern);
+ * without opts no word is cut.  encodeBatch(docs,
  * opts) encodes many documents in one call.  new MergeEncoder(engine, model,
  * { specialTokens: { '<|endoftext|>': id, ... } | Map of string or Uint8Array to id })
  * matches those strings on the raw bytes: each is one token and the text between
@@ -21,7 +22,7 @@
 import { native } from './native.js';
 
 const WORDS_MASK = 1;
-const WORDS_MODES = { heuristic: 2, gpt4: 3 };
+const WORDS_MODES = { heuristic: 2, gpt4: 3, cl100k: 4 };
 
 /** { bytes, offsets: Float64Array } of an array of Uint8Array laid end to end, or of one buffer with its offsets. */
 export function flattenDocuments(docs, offsets) {
@@ -124,7 +125,7 @@ export class MergeEncoder {
             return run(ws, WORDS_MASK);
         }
         if (!Object.prototype.hasOwnProperty.call(WORDS_MODES, words)) {
-            throw new TypeError("encodeBytes: words must be 'gpt4' or 'heuristic'");
+            throw new TypeError("encodeBytes: words must be 'gpt4', 'heuristic' or 'cl100k'");
         }
         return run(null, WORDS_MODES[words]);
     }
@@ -150,7 +151,7 @@ export class MergeEncoder {
             mode = WORDS_MASK;
         } else if (words !== null) {
             if (!Object.prototype.hasOwnProperty.call(WORDS_MODES, words)) {
-                throw new TypeError("encodeBatch: words must be 'gpt4' or 'heuristic'");
+                throw new TypeError("encodeBatch: words must be 'gpt4', 'heuristic' or 'cl100k'");
             }
             mode = WORDS_MODES[words];
         }

@@ -5,10 +5,19 @@
  * preTokenizeBytes(bytes) / preTokenize(text) return { bytes, wordStarts } like
  * the reference; BPETrainer.train(input, { preTokenizer }) accepts it the same
  * way (trainer.js:62-99).  Input must already be NFC (the reference
- * NFC-normalises first, which leaves NFC text unchanged).  Node 12 syntax.
+ * NFC-normalises first, which leaves NFC text unchanged).  Every call takes
+ * { rules: 'cl100k' } for the word starts of the cl100k_base split pattern instead
+ * (no normalisation belongs to it); the default, 'gpt4', is the rules above.
+ * Node 12 syntax.
  */
 import { native } from './native.js';
 import { flattenDocuments } from './merge-encoder.js';
+
+function rulesOf(opts, what) {
+    const rules = opts && opts.rules !== undefined && opts.rules !== null ? opts.rules : 'gpt4';
+    if (rules !== 'gpt4' && rules !== 'cl100k') throw new TypeError(what + ": rules must be 'gpt4' or 'cl100k'");
+    return rules;
+}
 
 export class GpuPreTokenizer {
     constructor(engine) {
@@ -16,10 +25,12 @@ export class GpuPreTokenizer {
         this._engine = engine;
     }
 
-    preTokenizeBytes(rawBytes) {
+    preTokenizeBytes(rawBytes, opts) {
+        const rules = rulesOf(opts, 'preTokenizeBytes');
         if (!rawBytes || rawBytes.length === 0) return { bytes: new Uint8Array(0), wordStarts: new Uint8Array(0) };
         const bytes = rawBytes instanceof Uint8Array ? rawBytes : new Uint8Array(rawBytes);
-        const wordStarts = native().pretokenizeGpt4(this._engine.device, bytes);
+        const wordStarts = rules === 'cl100k' ? native().pretokenizeCl100k(this._engine.device, bytes)
+            : native().pretokenizeGpt4(this._engine.device, bytes);
         return { bytes, wordStarts };
     }
 
@@ -28,14 +39,16 @@ export class GpuPreTokenizer {
      * Uint8Array with its D + 1 offsets.  Returns { bytes, wordStarts, offsets } over the
      * concatenation; each document's part is exactly preTokenizeBytes of it alone.
      */
-    preTokenizeBatch(docs, offsets) {
+    preTokenizeBatch(docs, offsets, opts) {
+        const rules = rulesOf(opts, 'preTokenizeBatch');
         const flat = flattenDocuments(docs, offsets);
-        const wordStarts = native().pretokenizeGpt4Batch(this._engine.device, flat.bytes, flat.offsets);
+        const wordStarts = rules === 'cl100k' ? native().pretokenizeCl100kBatch(this._engine.device, flat.bytes, flat.offsets)
+            : native().pretokenizeGpt4Batch(this._engine.device, flat.bytes, flat.offsets);
         return { bytes: flat.bytes, wordStarts: wordStarts, offsets: flat.offsets };
     }
 
-    preTokenize(text) {
+    preTokenize(text, opts) {
         if (!text || text.length === 0) return { bytes: new Uint8Array(0), wordStarts: new Uint8Array(0) };
-        return this.preTokenizeBytes(new Uint8Array(Buffer.from(text, 'utf8')));
+        return this.preTokenizeBytes(new Uint8Array(Buffer.from(text, 'utf8')), opts);
     }
 }
