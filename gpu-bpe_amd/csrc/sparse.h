@@ -928,6 +928,9 @@ __device__ __forceinline__ uint32_t* pair_word(ZSegState* zg) { return &zg->pad[
 //    bound" true.
 //  * Every read of the zone buffers here is done before the word is stored, and the
 //    zone workgroup stores to neither buffer before it saw the word.
+//  * After an accepting verdict it also adds merge 2's stale-tail and stale-window
+//    pairs, when that tail lies inside merge 1's window (mc2 <= m; below): two
+//    mc2-long chains of LDS compare-and-swaps that were the zone workgroup's.
 template <typename S, int BT, int NT>
 __device__ __forceinline__ void pair_churn(DevState* st, const DevState& gs, uint32_t z, const S* __restrict__ zc,
                                            const S* __restrict__ zo, ZSegState* zg, ZoneLds<S, BT>& L, LdsTab<NT>& ltab,
@@ -952,22 +955,26 @@ __device__ __forceinline__ void pair_churn(DevState* st, const DevState& gs, uin
     if (t == 0)
         h2 = __hip_atomic_load(reinterpret_cast<const uint64_t*>(&tb.slots[h2i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     S* xs = reinterpret_cast<S*>(L.xv);   // xs[i] = zone position lim - 2 + i, i in [0, mc + 2)
-    {   // both ranges in one round trip (8 loads in flight per thread)
+    S* s2s = xs + (mc + 2u);              // s2s[i] = zone position lim - 2 mc2 + i, i in [0, mc2 + 1): merge 2's window source
+    {   // the three ranges in one round trip (12 loads in flight per thread)
         const S* tsrc = zc + (lim - 2u);
         const S* wsrc = zo + win_src0(gs, mc);
+        const S* ssrc = zc + (lim - 2u * mc2);   // (>= 0: sel_inline's zone rule for the second merge; mc2 <= mc)
         for (uint32_t i0 = t; i0 < mc + 2u; i0 += 4u * BT) {
-            S v[4], w[4];
+            S v[4], w[4], q[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const uint32_t i = i0 + (uint32_t)u * BT;
                 v[u] = i < mc + 2u ? tsrc[i] : (S)0;
                 w[u] = i < mc ? wsrc[i] : (S)0;
+                q[u] = i < mc2 + 1u ? ssrc[i] : (S)0;
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const uint32_t i = i0 + (uint32_t)u * BT;
                 if (i < mc + 2u) xs[i] = v[u];
                 if (i < mc) L.wb[i] = w[u];
+                if (i < mc2 + 1u) s2s[i] = q[u];
             }
         }
     }
@@ -1074,9 +1081,67 @@ __device__ __forceinline__ void pair_churn(DevState* st, const DevState& gs, uin
         KT(8);
     }
     lds_flush<NT / BT>(lt, tb, st);
+    // ── merge 2's stale tail and stale window, off the zone workgroup's chain ──
+    // Merge 1's output is its kept survivors, then its window (L.wb[woff, mc), m symbols).  When
+    // mc2 <= m, merge 2's tail [z1 - mc2, z1) lies inside that window; the symbol before the window
+    // is position lim - 1 (xl1: kept and not rewritten, or the launch was rejected), and the one
+    // before that matters only as "is its token a2", which position lim - 2 answers: were it a
+    // merge-1 B-side, the symbol in its place would hold nw, and b is not a2 either.  zone_two
+    // tests the same condition on the same m and leaves both sets of pairs to this workgroup.
+    if (!rej && mc2 <= m) {   // (workgroup-uniform)
+        __shared__ uint32_t s_cm2[BT / 64];
+        const uint32_t a2 = s2.a, b2 = s2.b, n2 = nw + 1u, j0 = m - mc2;   // j0: the window index of position lim2
+        __syncthreads();   // (the flush's reads of the table are done)
+        lds_clear(lt);
+        auto Wn = [&](uint32_t j) -> uint32_t { return L.wb[woff + j]; };                           // output position Kz + j
+        auto Wp = [&](uint32_t j) -> uint32_t { return j ? (uint32_t)L.wb[woff + j - 1u] : xl1; };   // ... Kz + j - 1
+        uint32_t sv = 0;   // the tail's survivors: every position that is no merge-2 B-side
+        for (uint32_t j = j0 + t; j < m; j += BT) sv += (Wn(j) == b2 && (Wp(j) & TM) == a2) ? 0u : 1u;
+        sv = wave_sum_u32(sv);
+        if (lane == 0) s_cm2[wid] = sv;
+        __syncthreads();
+        uint32_t m2 = 0;
+#pragma unroll
+        for (int w2 = 0; w2 < BT / 64; ++w2) m2 += s_cm2[w2];
+        for (uint32_t jb = j0 + t; jb < m; jb += 4u * BT) {   // the tail's old pairs destroyed
+            uint32_t kq[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t j = jb + (uint32_t)k * BT, jc = j < m ? j : j0;
+                const uint32_t xi = Wn(jc), tp = Wp(jc) & TM, ti = xi & TM;
+                kq[k] = (j < m && !(xi & WS) && tp && ti && ((tp << 16) | ti) != pid2) ? (tp << 16) | ti : 0u;
+            }
+            lds_addk<4>(lt, tb, st, kq, 0xFFFFFFFFu);
+        }
+        // left of merge 2's window: its last kept survivor.  Position lim2 - 1 unless that is a B-side (then
+        // its A-side, which reads n2); it reads n2 as well when position lim2 is its B-side
+        const uint32_t p1 = Wp(j0), p2 = j0 >= 2u ? Wn(j0 - 2u) : (j0 == 1u ? xl1 : (uint32_t)xs[0]);
+        const bool bs1 = p1 == b2 && (p2 & TM) == a2, h0 = Wn(j0) == b2 && (p1 & TM) == a2;
+        const uint32_t xk = (bs1 || h0) ? n2 : (p1 & TM);
+        // the window = the last m2 source symbols, with merge 1's A-side rewrites (a before a B-side b reads nw)
+        const uint32_t woff2 = mc2 - m2;
+        auto S2 = [&](uint32_t q) -> uint32_t {
+            const uint32_t xp = s2s[q], xn = s2s[q + 1u];
+            return ((xp & TM) == a && xn == b) ? (nw | (xp & WS)) : xp;
+        };
+        for (uint32_t jb = t; jb < m2; jb += 4u * BT) {
+            uint32_t kq[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t j = jb + (uint32_t)k * BT;
+                kq[k] = 0u;
+                if (j < m2) {
+                    const uint32_t x1 = S2(woff2 + j), x0 = j ? S2(woff2 + j - 1u) & TM : xk;
+                    if (!(x1 & WS) && x0 && (x1 & TM)) kq[k] = (x0 << 16) | (x1 & TM);
+                }
+            }
+            lds_addk<4>(lt, tb, st, kq, 1u);
+        }
+        lds_flush<NT / BT>(lt, tb, st);
+    }
     if (t == 0) {
         KT(4);
-        atomicAdd(bytes, (uint64_t)sizeof(S) * (2ull * mc + 2u));   // the tail and the window source read
+        atomicAdd(bytes, (uint64_t)sizeof(S) * (2ull * mc + mc2 + 3u));   // the tail and both window sources read
     }
 }
 
@@ -1097,7 +1162,8 @@ __device__ __forceinline__ void pair_churn(DevState* st, const DevState& gs, uin
 //    copies the window into its LDS zone, and reads the verdict word once merge 1
 //    is assembled (first load issued before the assembly, then the body's poll).
 //    It sends no merge-2 delta to the global table and stores to neither zone
-//    buffer before it saw the word.
+//    buffer before it saw the word.  Merge 2's stale-tail and window pairs are the
+//    churn workgroup's too when mc2 <= m; this workgroup still copies the window.
 //  * zo ends as the first merge's output with the second's A-side rewrites (a later
 //    window reads it), zc as the second's output.  Rejected: the first merge's
 //    output goes to zo and its rewrites to zc, as zone_one leaves them.
@@ -1357,7 +1423,10 @@ __device__ __forceinline__ void zone_two(DevState* st, DevState* zst, const DevS
         const uint32_t surv = inb & ~hitm, keep2 = surv & below;
         const uint32_t rw2 = ((hitm >> 1) | (h_32 << (ZPT - 1))) & inb;
         uint32_t rel = ((uint32_t)hbits | (uint32_t)(hbits >> 1) | (uint32_t)(hbits >> 2)) & below & inb;
-        for (uint32_t ib = (lim2 > 1u ? lim2 : 1u) + t; ib < z1; ib += 4u * BT) {   // stale tail: old pairs destroyed
+        // (ref mode, mc2 <= m: the tail lies inside merge 1's window, and the churn workgroup adds its
+        // pairs and the window's — pair_churn tests the same condition on the same m)
+        const bool own2 = EXACT || mc2 > m;
+        for (uint32_t ib = (lim2 > 1u ? lim2 : 1u) + t; own2 && ib < z1; ib += 4u * BT) {   // stale tail: old pairs destroyed
             uint32_t kq[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -1439,10 +1508,10 @@ __device__ __forceinline__ void zone_two(DevState* st, DevState* zst, const DevS
                         const uint32_t x1 = wb2[woff2 + j];
                         const uint32_t x0 = j ? (uint32_t)wb2[woff2 + j - 1] : xk;
                         xs[swz(Kz2 + j)] = (S)x1;
-                        if (!(x1 & WS) && (x0 & TM) && (x1 & TM)) kq[k] = ((x0 & TM) << 16) | (x1 & TM);
+                        if (own2 && !(x1 & WS) && (x0 & TM) && (x1 & TM)) kq[k] = ((x0 & TM) << 16) | (x1 & TM);
                     }
                 }
-                lds_addk<4>(lt, tb, st, kq, 1u);
+                if (own2) lds_addk<4>(lt, tb, st, kq, 1u);
             }
         }
         __syncthreads();
@@ -1469,7 +1538,8 @@ __device__ __forceinline__ void zone_two(DevState* st, DevState* zst, const DevS
 // source [n - 2mc - Bp, + mc) of the zone's other buffer to `wtmp`.
 // With `zst` (zone <= ZMAX), block nbody runs the whole zone pass (zone_one) and
 // there are no copy blocks: one launch merges body and zone.
-// A paired launch (the 256-thread form, Sel2) tests each bitmap word for both
+// A paired launch (the 256-thread form and the 512-thread one for zones of 8K-16K
+// symbols, Sel2) tests each bitmap word for both
 // merges, merges the first's candidate sectors, then — once the zone workgroup
 // accepted the second (ref mode) — the second's.  A sector is owned by one
 // workgroup for both, so its two merges run in order.
@@ -1489,7 +1559,9 @@ using BodyCand = BodyCandT<SP_CAP>;
 // (u32 zones: 2,048 slots, so two workgroups still fit a CU's LDS — the paired form's
 // grid is the CU count + 2 (zone, churn, body), resident at once at two workgroups
 // per CU: the zone and the body workgroups wait on the churn workgroup, which waits
-// on nobody, and blocks 0 and 1 are dispatched first)
+// on nobody, and blocks 0 and 1 are dispatched first.  That is the 256-thread form;
+// the 512-thread form for zones of 8K-16K symbols takes 97 KB (u16) / 136 KB (u32),
+// one workgroup per CU, and its body grid is capped at the CU count - 2 instead)
 template <typename S> constexpr int zp_lt() { return sizeof(S) == 2 ? 4096 : 2048; }
 template <typename S, int BT, int ZLT>
 struct ZoneWg {
@@ -1508,7 +1580,11 @@ union BodyLds {   // body workgroups use the candidate arrays, the zone workgrou
 // (with both, every form spilled to scratch)
 // zb0 / zb1: the zone buffers by the step's parity (zb0 holds the zone at merge 0
 // of the step); a merge of odd index finds it in zb1
-template <typename S, bool EXACT, int BT, int ZPT = ZoneDim<S, BT>::ZPT, bool ZSEG = false>
+// PAIR: the launch may run two merges — the late form (zone_one in 256
+// threads), and the 512-thread form with 32 zone symbols per thread for zones of
+// 8K-16K symbols, launched only for steps that may pair (launch_body's 1022; the
+// unpaired steps of that range keep the two-segment form)
+template <typename S, bool EXACT, int BT, int ZPT = ZoneDim<S, BT>::ZPT, bool ZSEG = false, bool PAIR = (BT == 256 && !ZSEG)>
 __global__ __launch_bounds__(BT) void k_body(DevState* st, uint32_t round, S* __restrict__ body, uint2* __restrict__ sec,
                                               uint32_t* __restrict__ bits, uint32_t W, uint32_t wpg,
                                               uint32_t* __restrict__ sig, Table tb, uint32_t nbody,
@@ -1518,8 +1594,8 @@ __global__ __launch_bounds__(BT) void k_body(DevState* st, uint32_t round, S* __
                                               uint32_t* __restrict__ grpsum, uint64_t* __restrict__ wg_bytes,
                                               Table dtb, SelShard sh, uint32_t* __restrict__ lmul,
                                               ZSegState* __restrict__ zg = nullptr) {
+    static_assert(!(PAIR && ZSEG), "the segment forms run one merge per launch");
     constexpr int KB_LT = ZSEG ? 4096 : LTAB_T;   // (4096 for every 1024-thread form: no change on C5 / 1 GiB / C2, r4)
-    constexpr bool PAIR = BT == 256 && !ZSEG;     // paired launches: the late form (zone_one in 256 threads)
     __shared__ LdsTab<KB_LT> lt;
     __shared__ BodyLds<S, BT, PAIR ? zp_lt<S>() : 1> u;
     // per wave: its sector's new signature bits (the 1024-thread forms: the early,

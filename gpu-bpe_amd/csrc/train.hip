@@ -334,7 +334,13 @@ int trainer_step_once(gbpe_trainer* t, uint32_t max_merges, uint32_t* merges_out
         if (sg.bt == 1024 && t->u16 && zn <= 16384u) sg.bt = 1023;
         sg.zone1 = zn <= (t->u16 ? zone_max<uint16_t>(sg.bt) : zone_max<uint32_t>(sg.bt)) ? 1u : 0u;
         // a zone of 16K-1M symbols: 16K-symbol segments inside k_body (its ZSEG form)
-        if (t->zseg.p && zn > SP_ZSEG_LO && zn <= NSEG_MAX * 16384u) {
+        // ... except a zone of 8K-16K symbols in a step that may pair: one 512-thread zone
+        // workgroup of 32 symbols per thread, two merges per launch (launch_body 1022)
+        const bool p16 = t->pair_on && t->pair16_on && t->zseg.p && k >= 2 && zn > SP_ZSEG_LO && zn <= SP_PAIR16_HI;
+        if (p16) {
+            sg.bt = 1022;
+            sg.zone1 = 1;
+        } else if (t->zseg.p && zn > SP_ZSEG_LO && zn <= NSEG_MAX * 16384u) {
             sg.seg8 = zn <= NSEG_MAX * 8192u;
             sg.zone1 = (uint32_t)gbpe_div_up(zn, sg.seg8 ? 8192u : 16384u);
         }
@@ -346,8 +352,10 @@ int trainer_step_once(gbpe_trainer* t, uint32_t max_merges, uint32_t* merges_out
         // the window copy's) workgroups beside the body's, past the CU count, wait for
         // a CU to drain (C5 merges 512-8K: the last one started 14-19 us late) — so
         // the body takes the CUs the others leave
-        const uint32_t extra = sg.zone1 ? sg.zone1 : sg.copy;
-        if (sg.bt >= 1023 && extra && sg.body + extra > t->body_cap && 2 * extra <= t->body_cap)
+        // (the paired form of that range holds one workgroup per CU and waits on its churn
+        // workgroup: zone, churn and body workgroups are resident together)
+        const uint32_t extra = p16 ? ((t->flags & GBPE_TRAIN_EXACT_COMPACTION) ? 1u : 2u) : sg.zone1 ? sg.zone1 : sg.copy;
+        if (sg.bt >= 1022 && extra && sg.body + extra > t->body_cap && 2 * extra <= t->body_cap)
             body_grid(t, sg.bt, &sg.body, &sg.wpg, t->body_cap - extra, &sg.sub);
         // late steps (a zone of <= 16K symbols): a smaller k_refresh grid —
         // a late merge dirties a few blocks, and fewer workgroups dispatch and drain
@@ -374,7 +382,7 @@ int trainer_step_once(gbpe_trainer* t, uint32_t max_merges, uint32_t* merges_out
         sg.refresh = g_refresh;
         // paired launches: the late zone_one form, two merges per launch
         // when the table's top two allow it
-        sg.pair = t->pair_on && sg.zone1 == 1 && sg.bt == 256 && t->zseg.p && k >= 2;
+        sg.pair = t->pair_on && sg.zone1 == 1 && (sg.bt == 256 || sg.bt == 1022) && t->zseg.p && k >= 2;
     }
     // a paired step needs fewer launches than merges: sized by the last paired step's
     // rate (+2); launches past the step's budget are no-ops, and a step whose launches

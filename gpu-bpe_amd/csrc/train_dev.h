@@ -178,10 +178,10 @@ __device__ __forceinline__ void kt_put(uint32_t round, uint32_t wg, int i, unsig
 #define KT(i) kt_put(round, blockIdx.x, (i), wall_clock64())
 #define KTV(i, v) kt_put(round, blockIdx.x, (i), (v))
 #define KTR(i) kt_put(round, KT_WG + blockIdx.x, (i), wall_clock64())
-// per-wave stamps of the zone workgroup (lane 0 of every wave): rows KT_WG - 8 + wave
-#define KTW(i) do { if ((threadIdx.x & 63) == 0) kt_put(round, KT_WG - 8u + (threadIdx.x >> 6), (i), wall_clock64()); } while (0)
+// per-wave stamps of the zone workgroup (lane 0 of its first four waves): rows KT_WG - 8 + wave
+#define KTW(i) do { if ((threadIdx.x & 63) == 0 && threadIdx.x < 256) kt_put(round, KT_WG - 8u + (threadIdx.x >> 6), (i), wall_clock64()); } while (0)
 // ... and of the paired launch's churn workgroup: rows KT_WG - 4 + wave
-#define KTC(i) do { if ((threadIdx.x & 63) == 0) kt_put(round, KT_WG - 4u + (threadIdx.x >> 6), (i), wall_clock64()); } while (0)
+#define KTC(i) do { if ((threadIdx.x & 63) == 0 && threadIdx.x < 256) kt_put(round, KT_WG - 4u + (threadIdx.x >> 6), (i), wall_clock64()); } while (0)
 #else
 #define KTW(i) ((void)0)
 #define KTC(i) ((void)0)

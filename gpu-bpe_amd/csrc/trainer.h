@@ -94,6 +94,7 @@ struct gbpe_trainer {
     bool pair_on = true;         // paired launches (GBPE_DEBUG pair=0: one merge per launch)
     double pair_rate = 0.5;      // second merges per launch of the last paired step (sizes the next step's launches)
     uint64_t pair_done = 0;      // merges run as the second of a launch (stats)
+    bool pair16_on = true;       // ... also in zones of 8K-16K symbols (launch_body 1022; GBPE_DEBUG pseg=0: the two-segment form)
     uint32_t pair_prej = 0;      // GBPE_DEBUG prej=k (tests): the verdict rejects every k-th candidate (0: off)
     uint32_t ptrace = 0;         // GBPE_DEBUG ptrace=1: every step's form and pairing on stderr
     GbpeArray<uint32_t> d_clog;  // GBPE_SPARSE_TRACE: per-merge candidate / hit sectors
@@ -318,13 +319,16 @@ struct SpGrid {
     uint32_t sub = 1;     // k_body workgroups per bitmap word (wpg = 1)
     bool seg8 = false;    // zone segments of 8K symbols (1024 threads x 8), else 16K
     uint32_t zone1;   // zone workgroups inside k_body: 1 = zone_one, >= 2 = zone_seg segments, 0 = multi-tile passes
-    int bt;       // k_body workgroup size (256 or 1024)
-    bool pair = false;   // launches may run two merges (zone_one in the 256-thread form)
+    int bt;       // k_body workgroup size (256 or 1024; 1023 / 1022: launch_body)
+    bool pair = false;   // launches may run two merges (the 256-thread form and the 512 x 32 one)
 };
+
+// zones up to this many symbols pair in one 512-thread zone workgroup (launch_body 1022: 512 x 32)
+constexpr uint32_t SP_PAIR16_HI = 16384;
 
 template <typename S>
 uint32_t zone_max(int bt) {
-    return bt == 1023 ? 1024u * 16u : bt == 1024 ? ZoneDim<S, 1024>::ZMAX : ZoneDim<S, 256>::ZMAX;
+    return bt == 1023 ? 1024u * 16u : bt == 1022 ? SP_PAIR16_HI : bt == 1024 ? ZoneDim<S, 1024>::ZMAX : ZoneDim<S, 256>::ZMAX;
 }
 // k_body grid: bitmap words per workgroup (>= the measured best 16 / 32 at C2 size),
 // at most `cap` workgroups (default: body_cap, one per CU)
@@ -361,10 +365,13 @@ inline void body_grid(const gbpe_trainer* t, int bt, uint32_t* nbody, uint32_t* 
 // bt: 256, 1024, or 1023 = 1024 threads with 16 zone symbols each (u16 zones of
 // 8K-16K symbols: half the per-thread zone work of the 32K form; 1 GiB en1g
 // 1.017 -> 0.963 s.  1024 threads x 8 for zones <= 8K instead of 256 x 32 was
-// slower: C2 0.66 vs 0.61 s)
+// slower: C2 0.66 vs 0.61 s), or 1022 = the paired form of 512 threads x 32 zone
+// symbols (zones of 8K-16K symbols in steps that may pair)
 template <typename S, bool EXACT, typename... A>
 void launch_body(int bt, uint32_t grid, hipStream_t s, A... args) {
-    if (bt == 2048)   // zone segments inside k_body (the ZSEG form, 1024 threads)
+    if (bt == 1022)
+        hipLaunchKernelGGL((k_body<S, EXACT, 512, 32, false, true>), dim3(grid), dim3(512), 0, s, args...);
+    else if (bt == 2048)   // zone segments inside k_body (the ZSEG form, 1024 threads)
         hipLaunchKernelGGL((k_body<S, EXACT, 1024, 16, true>), dim3(grid), dim3(1024), 0, s, args...);
     else if (bt == 2049)   // ... with 8K-symbol segments (zones <= 512K)
         hipLaunchKernelGGL((k_body<S, EXACT, 1024, 8, true>), dim3(grid), dim3(1024), 0, s, args...);
@@ -393,7 +400,7 @@ int launch_merge_sparse(gbpe_trainer* t, uint32_t round, hipStream_t s, const Sp
     sh.prej = t->pair_prej;
     // a paired launch under the reference compaction: block 1 is the churn workgroup (pair_churn),
     // right after the zone workgroup; both add their bytes to the counter after the body's
-    sh.churn = (g.pair && !exact && bt == 256 && z1 == 1) ? 1u : 0u;
+    sh.churn = (g.pair && !exact && (bt == 256 || bt == 1022) && z1 == 1) ? 1u : 0u;
     const uint32_t gb = g.body + (g.zone1 ? g.zone1 : g.copy) + sh.churn;
     if ((uint64_t)g.body + 1 > t->wg_bytes.cap)   // k_body's per-workgroup byte counters (and the zone's after them)
         return gbpe_set_error(t->ctx, GBPE_E_INTERNAL, "k_body grid (%u) above its byte counters (%llu)", g.body,
@@ -1222,6 +1229,7 @@ int trainer_config(gbpe_trainer* t, gbpe_ctx* ctx, const gbpe_train_opts* opts) 
     // in-loop table growth off, the multi-tile k_delta threshold, the zone target
     t->lex_on = gbpe_debug_knob("lexicon", 1) != 0;
     t->pair_on = gbpe_debug_knob("pair", 1) != 0;
+    t->pair16_on = gbpe_debug_knob("pseg", 1) != 0;
     t->pair_prej = (uint32_t)std::max<long>(0, gbpe_debug_knob("prej", 0));
     t->ptrace = (uint32_t)gbpe_debug_knob("ptrace", 0);
     t->rehash_on = gbpe_debug_knob("rehash", 1) != 0;

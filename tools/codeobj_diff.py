@@ -12,6 +12,12 @@ dropped, so only the instructions and their operands are compared (branches are
 relative: moving a kernel does not change them).  Prints the functions that
 exist on one side only, those whose instructions differ, and a summary line;
 exit status 1 when anything differs.
+
+    --rename 'REGEX=REPL'   applied to the second library's symbols before they are
+                            matched (a kernel that gained a template argument)
+    --notes REGEX           also print LDS bytes, scratch bytes, VGPRs, SGPRs and spills
+                            (llvm-readelf --notes) of the second library's kernels whose
+                            symbol matches
 """
 import hashlib
 import os
@@ -73,8 +79,35 @@ def functions(lib):
     return fns
 
 
+def notes(lib, pat):
+    """resource usage of the kernels whose symbol matches pat, from the code objects' metadata notes"""
+    with tempfile.TemporaryDirectory() as tmp:
+        for i, co in enumerate(code_objects(lib, tmp)):
+            path = os.path.join(tmp, f"co{i}.o")
+            open(path, "wb").write(co)
+            out = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", path], check=True, capture_output=True,
+                                 text=True).stdout
+            for blk in out.split("- .agpr_count")[1:]:
+                f = lambda k: re.search(r"\.%s:\s+(\S+)" % k, blk).group(1)
+                if re.search(pat, f("name")):
+                    print(f"notes: {f('name')}: lds {f('group_segment_fixed_size')} scratch {f('private_segment_fixed_size')} "
+                          f"vgpr {f('vgpr_count')} sgpr {f('sgpr_count')} vgpr spills {f('vgpr_spill_count')} "
+                          f"sgpr spills {f('sgpr_spill_count')}")
+
+
 def main():
+    rename, pat = None, None
+    while len(sys.argv) > 3 and sys.argv[1] in ("--rename", "--notes"):
+        if sys.argv[1] == "--rename":
+            rename = sys.argv[2].split("=", 1)
+        else:
+            pat = sys.argv[2]
+        del sys.argv[1:3]
     a, b = functions(sys.argv[1]), functions(sys.argv[2])
+    if rename:
+        b = {re.sub(rename[0], rename[1], k): v for k, v in b.items()}
+    if pat:
+        notes(sys.argv[2], pat)
     only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
     differ = sorted(k for k in set(a) & set(b) if a[k] != b[k])
     for k in only_a:
