@@ -158,7 +158,7 @@ __host__ __device__ static inline uint64_t gbpe_div_up(uint64_t a, uint64_t b) {
 // Debug / test overrides: GBPE_DEBUG="key=value,key=value" (DESIGN §6 lists the
 // keys); every other tuning value is a compiled default
 constexpr const char* kGbpeDebugKeys[] = {
-    "lexicon", "lex_check", "rehash", "delta_mt", "zt", "rfl", "rflz", "lxwg", "lxtwo", "pair", "pseg", "prej", "poison",
+    "lexicon", "lex_check", "rehash", "delta_mt", "zt", "rfl", "rflz", "lxwg", "lxtwo", "pair", "pseg", "prej", "zsmax", "zs32", "poison",
     "encode_slice", "decode_slice", "dec_plain", "me_cs", "htime", "ptrace", "rtime",
 };
 

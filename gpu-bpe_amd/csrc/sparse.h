@@ -506,7 +506,7 @@ __device__ __forceinline__ void zone_one(DevState* st, DevState* zst, uint32_t z
     }
 }
 
-// ── segmented zone pass (zones of 32K-1M symbols) ──
+// ── segmented zone pass (zones of 8K-2M symbols; 16-bit symbols: up to 4M in 32K-symbol segments) ──
 // A zone too large for one workgroup but far smaller than the stream (merges
 // ~500-8000 at 1 GiB) is cut into segments of BT x ZPT = 16K symbols, one
 // 1024-thread workgroup each (blocks [0, nz) of k_body).  Two phases:
@@ -526,7 +526,9 @@ __device__ __forceinline__ void zone_one(DevState* st, DevState* zst, uint32_t z
 //    read of the other buffer (the window source) happened in phase A, before
 //    any segment passes phase B's sweep, so no store overwrites an unread source.
 //  Every zone workgroup waits only on zone workgroups, which never wait on body
-//  workgroups: with nz <= 64 workgroups they all become resident.
+//  workgroups: they are blocks [0, nz) of the launch, dispatched first, one per CU
+//  (the 1024-thread form's LDS), and the host keeps nz <= max(64, CUs / 2) <= NSEG_MAX
+//  (zseg_cap), so they all become resident.
 // k_refresh zeroes the granules for the next merge (tag = 1).
 template <typename S, bool EXACT, int BT, int NT, int ZPT>
 __device__ __forceinline__ void zone_seg(DevState* st, DevState* zst, const DevState& gs, const DevState& zs, S* __restrict__ zc,
@@ -679,39 +681,71 @@ __device__ __forceinline__ void zone_seg(DevState* st, DevState* zst, const DevS
         zc[gi0 + k] = (S)(nw | (((wsm >> k) & 1u) ? WS : 0u));
     }
     // B: every segment's granules (one wave, relaxed sweeps, s_sleep between)
+    // (lane l sweeps segments l and, above 64 segments, l + 64: all of a lane's loads issue before the tag test)
     if (wid == 0) {
-        uint32_t gk = 0, gt = 0, gl = 0;
-        for (uint32_t it = 0;; ++it) {
-            bool ok = true;
-            if ((uint32_t)lane < nz) {
-                const unsigned long long x0 = __hip_atomic_load(&zg->gran[lane][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const unsigned long long x1 = __hip_atomic_load(&zg->gran[lane][1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const unsigned long long x2 = __hip_atomic_load(&zg->gran[lane][2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                ok = (x0 >> 32) == 1u && (x1 >> 32) == 1u && (x2 >> 32) == 1u;
-                gk = (uint32_t)x0;
-                gt = (uint32_t)x1;
-                gl = (uint32_t)x2;
+        const uint32_t sh = (uint32_t)lane + 64u;     // this lane's segment of the upper half
+        const bool in = (uint32_t)lane < nz, inh = sh < nz;
+        const bool up = nz > 64u;                     // (wave-uniform)
+        uint32_t gk = 0, gt = 0, gl = 0, hk = 0, ht = 0, hl = 0;
+        // (two forms of one loop: at most 64 segments keep the single-half sweep, instruction for instruction)
+        auto sweep = [&](auto two) {
+            constexpr bool TWO = decltype(two)::value;
+            for (uint32_t it = 0;; ++it) {
+                bool ok = true;
+                if (in) {
+                    const unsigned long long x0 = __hip_atomic_load(&zg->gran[lane][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const unsigned long long x1 = __hip_atomic_load(&zg->gran[lane][1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const unsigned long long x2 = __hip_atomic_load(&zg->gran[lane][2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    ok = (x0 >> 32) == 1u && (x1 >> 32) == 1u && (x2 >> 32) == 1u;
+                    gk = (uint32_t)x0;
+                    gt = (uint32_t)x1;
+                    gl = (uint32_t)x2;
+                    if constexpr (TWO) {
+                        if (inh) {
+                            const unsigned long long y0 = __hip_atomic_load(&zg->gran[sh][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            const unsigned long long y1 = __hip_atomic_load(&zg->gran[sh][1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            const unsigned long long y2 = __hip_atomic_load(&zg->gran[sh][2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            ok = ok && (y0 >> 32) == 1u && (y1 >> 32) == 1u && (y2 >> 32) == 1u;
+                            hk = (uint32_t)y0;
+                            ht = (uint32_t)y1;
+                            hl = (uint32_t)y2;
+                        }
+                    }
+                }
+                if (__all(ok)) break;
+                if (it > ZSEG_SPIN) {
+                    if (lane == 0) atomicOr(&st->err, ERR_SPIN);
+                    break;
+                }
+                __builtin_amdgcn_s_sleep(1);
             }
-            if (__all(ok)) break;
-            if (it > ZSEG_SPIN) {
-                if (lane == 0) atomicOr(&st->err, ERR_SPIN);
-                break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-        const bool in = (uint32_t)lane < nz;
+        };
+        if (up) sweep(std::true_type());
+        else sweep(std::false_type());
+        // prefix = kept symbols of the segments below seg; totals over both halves
         uint32_t sp = in && (uint32_t)lane < seg ? gk : 0u, sk = in ? gk : 0u, stt = in ? gt : 0u;
+        if (up) {
+            sp += inh && sh < seg ? hk : 0u;
+            sk += inh ? hk : 0u;
+            stt += inh ? ht : 0u;
+        }
         sp = wave_sum_u32(sp);
         sk = wave_sum_u32(sk);
         stt = wave_sum_u32(stt);
         const unsigned long long hm = __ballot(in && (gl >> 31));
+        const unsigned long long hmh = up ? __ballot(inh && (hl >> 31)) : 0ull;
         if (lane == 0) {
             s_pre = sp;
             s_kz = sk;
             s_m = EXACT ? 0u : stt;
             s_x0 = 0u;
         }
-        if (hm && lane == 63 - __clzll(hm)) s_x0 = gl & 0x7FFFFFFFu;   // the last kept survivor overall
+        // the last kept survivor overall: of the highest segment that kept a symbol, the upper half first
+        if (hmh) {
+            if (lane == 63 - __clzll(hmh)) s_x0 = hl & 0x7FFFFFFFu;
+        } else if (hm && lane == 63 - __clzll(hm)) {
+            s_x0 = gl & 0x7FFFFFFFu;
+        }
     }
     __syncthreads();
     if (t == 0) KT(8);

@@ -325,6 +325,7 @@ int trainer_step_once(gbpe_trainer* t, uint32_t max_merges, uint32_t* merges_out
     const bool timing = (t->flags & GBPE_TRAIN_TIMING) != 0;
     const bool sparse = t->sp;
     SpGrid sg{};
+    const uint32_t zn0 = sparse ? (uint32_t)t->n - hs->B : 0u;   // (ptrace) the zone's length at the step's start
     if (sparse) {
         const uint32_t zn = (uint32_t)t->n - hs->B;   // zone length (it only shrinks within a step)
         const uint64_t zt = gbpe_div_up(zn, TILE);
@@ -333,16 +334,22 @@ int trainer_step_once(gbpe_trainer* t, uint32_t max_merges, uint32_t* merges_out
         body_grid(t, sg.bt, &sg.body, &sg.wpg, 0, &sg.sub);
         if (sg.bt == 1024 && t->u16 && zn <= 16384u) sg.bt = 1023;
         sg.zone1 = zn <= (t->u16 ? zone_max<uint16_t>(sg.bt) : zone_max<uint32_t>(sg.bt)) ? 1u : 0u;
-        // a zone of 16K-1M symbols: 16K-symbol segments inside k_body (its ZSEG form)
+        // a zone of 16K-2M symbols: 16K-symbol segments inside k_body (its ZSEG form), at most
+        // zseg_max of them (128; zones <= 512K: 8K-symbol segments, the measured choice at 64)
         // ... except a zone of 8K-16K symbols in a step that may pair: one 512-thread zone
         // workgroup of 32 symbols per thread, two merges per launch (launch_body 1022)
         const bool p16 = t->pair_on && t->pair16_on && t->zseg.p && k >= 2 && zn > SP_ZSEG_LO && zn <= SP_PAIR16_HI;
         if (p16) {
             sg.bt = 1022;
             sg.zone1 = 1;
-        } else if (t->zseg.p && zn > SP_ZSEG_LO && zn <= NSEG_MAX * 16384u) {
-            sg.seg8 = zn <= NSEG_MAX * 8192u;
+        } else if (t->zseg.p && zn > SP_ZSEG_LO && zn <= t->zseg_max * 16384u &&
+                   !(t->u16 && t->zseg32 == 2 && zn > 64u * 16384u)) {
+            sg.seg8 = zn <= std::min<uint32_t>(t->zseg_max, 64u) * 8192u;
             sg.zone1 = (uint32_t)gbpe_div_up(zn, sg.seg8 ? 8192u : 16384u);
+        } else if (t->zseg.p && t->u16 && t->zseg32 && zn > SP_ZSEG_LO && zn <= t->zseg_max * 32768u) {
+            // (u16) 32K-symbol segments: zones above the 16K form's reach (zs32=2: above 1M)
+            sg.seg32 = true;
+            sg.zone1 = (uint32_t)gbpe_div_up(zn, 32768u);
         }
         sg.copy = (t->flags & GBPE_TRAIN_EXACT_COMPACTION) ? 0u : grid_persistent(t->ctx, gbpe_div_up(zn / 5 + 1, TPB * 8), 1);
         sg.zdelta = (uint32_t)(zt ? zt : 1);
@@ -424,10 +431,10 @@ int trainer_step_once(gbpe_trainer* t, uint32_t max_merges, uint32_t* merges_out
         t->pair_done += dbl;
         if (sg.pair && done > dbl) t->pair_rate = (double)dbl / (double)(done - dbl);
         if (t->ptrace)   // (diagnostic, GBPE_DEBUG ptrace=1) the step's form and pairing
-            fprintf(stderr, "[ptrace] merge %u zone %u zone1 %u bt %d pair %d launches %u done %u paired %u cand %u mc %u us %.1f\n",
-                    t->done, hs->n - hs->B, sg.zone1, sg.bt, sg.pair ? 1 : 0, nl, done, dbl,
+            fprintf(stderr, "[ptrace] merge %u zone %u zone1 %u bt %d pair %d launches %u done %u paired %u cand %u mc %u us %.1f zone0 %u\n",
+                    t->done, hs->n - hs->B, sg.zone1, sg.seg32 ? 2050 : sg.bt, sg.pair ? 1 : 0, nl, done, dbl,
                     hs->pair_cand, done ? t->h_log.p[(done - 1) * 4 + 3] : 0u,
-                    std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - hs0).count());
+                    std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - hs0).count(), zn0);
     }
     if (t->htime) {   // (diagnostic) host enqueue vs wait; "late": a zone of <= 16K symbols
         t->ht_pre += std::chrono::duration<double, std::micro>(h0 - hs0).count();

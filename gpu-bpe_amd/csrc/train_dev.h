@@ -149,14 +149,16 @@ __device__ __forceinline__ uint64_t win_src0(const DevState& g, uint32_t mc) {
 }
 
 // the zone segments' per-merge hand-off (zone_seg; k_refresh zeroes it)
-constexpr uint32_t NSEG_MAX = 64;   // one sweeping wave: one lane per segment
+constexpr uint32_t NSEG_MAX = 128;   // one sweeping wave: lane l reads segments l and l + 64
 constexpr uint32_t ZSEG_SPIN = 1u << 22;
 struct ZSegState {
     uint32_t ticket;
     uint32_t pad[15];
     unsigned long long gran[NSEG_MAX][4];   // {1, kept}, {1, tail survivors}, {1, last kept | has kept << 31}
 };
-constexpr uint32_t ZSEG_WORDS = 16 + NSEG_MAX * 8;   // u32 words k_refresh zeroes (ticket, granules)
+// u32 words k_refresh zeroes after a launch of nz zone segments: the ticket and those
+// segments' granules (nz <= 1: no segment form ran, the ticket word alone)
+__host__ __device__ constexpr uint32_t zseg_words(uint32_t nz) { return nz >= 2 ? 16u + (nz < NSEG_MAX ? nz : NSEG_MAX) * 8u : 1u; }
 
 // Phase timestamps of the sector-sparse kernels (diagnostic builds only:
 // -DGBPE_KTRACE; tools/ktrace.sh).  Every KT_EVERY-th merge, each workgroup
@@ -729,11 +731,19 @@ template <typename S, bool WIDE = false>
 __global__ __launch_bounds__(TPB) void k_refresh(DevState* st, uint32_t round, int finish, Table tb, S* __restrict__ cur,
                                                  const uint32_t* __restrict__ rwlist, DevState* zst,
                                                  uint32_t* __restrict__ clog = nullptr, FusedSel fs = FusedSel(),
-                                                 uint64_t* __restrict__ part = nullptr, uint32_t* __restrict__ zseg = nullptr) {
+                                                 uint64_t* __restrict__ part = nullptr, uint32_t* __restrict__ zseg = nullptr,
+                                                 uint32_t zseg_nz = 0) {
     (void)cur;
-    if (zseg && blockIdx.x == 0)   // ZSegState: ticket + granules of the next merge's zone segments
-        for (uint32_t i = threadIdx.x; i < ZSEG_WORDS; i += TPB)
-            if (i == 0 || i >= 16) zseg[i] = 0u;
+    // ZSegState: ticket + the granules this merge's zseg_nz zone segments wrote (the count is read with
+    // the other launch arguments, and the stores are predicated: no loop in block 0's chain)
+    const uint32_t nwz = zseg_words(zseg_nz);
+    if (zseg && blockIdx.x == 0) {
+#pragma unroll
+        for (uint32_t r = 0; r < (zseg_words(NSEG_MAX) + TPB - 1) / TPB; ++r) {
+            const uint32_t i = threadIdx.x + r * TPB;
+            if (i < nwz && (i == 0 || i >= 16)) zseg[i] = 0u;
+        }
+    }
     (void)rwlist;
     if (part && finish == 2 && threadIdx.x == 0) KTR(0);
     // this WG's contiguous run of blocks (<= TPB, one per thread): all flags (and,

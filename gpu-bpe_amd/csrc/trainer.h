@@ -95,6 +95,9 @@ struct gbpe_trainer {
     double pair_rate = 0.5;      // second merges per launch of the last paired step (sizes the next step's launches)
     uint64_t pair_done = 0;      // merges run as the second of a launch (stats)
     bool pair16_on = true;       // ... also in zones of 8K-16K symbols (launch_body 1022; GBPE_DEBUG pseg=0: the two-segment form)
+    uint32_t zseg_max = NSEG_MAX; // most zone segments of a k_body launch (zseg_cap; GBPE_DEBUG zsmax=K, 64: zones above 1M multi-tile)
+    uint32_t zseg32 = 1;         // u16 zones above zseg_max x 16K (1) or above 1M (2) in 32K-symbol segments, up to
+                                 // zseg_max of them (GBPE_DEBUG zs32; 0: off — with zsmax=64 the forms from before)
     uint32_t pair_prej = 0;      // GBPE_DEBUG prej=k (tests): the verdict rejects every k-th candidate (0: off)
     uint32_t ptrace = 0;         // GBPE_DEBUG ptrace=1: every step's form and pairing on stderr
     GbpeArray<uint32_t> d_clog;  // GBPE_SPARSE_TRACE: per-merge candidate / hit sectors
@@ -318,6 +321,7 @@ struct SpGrid {
     uint32_t wpg = 16;    // bitmap words per k_body workgroup
     uint32_t sub = 1;     // k_body workgroups per bitmap word (wpg = 1)
     bool seg8 = false;    // zone segments of 8K symbols (1024 threads x 8), else 16K
+    bool seg32 = false;   // ... of 32K symbols (1024 x 32, u16 only)
     uint32_t zone1;   // zone workgroups inside k_body: 1 = zone_one, >= 2 = zone_seg segments, 0 = multi-tile passes
     int bt;       // k_body workgroup size (256 or 1024; 1023 / 1022: launch_body)
     bool pair = false;   // launches may run two merges (the 256-thread form and the 512 x 32 one)
@@ -325,6 +329,18 @@ struct SpGrid {
 
 // zones up to this many symbols pair in one 512-thread zone workgroup (launch_body 1022: 512 x 32)
 constexpr uint32_t SP_PAIR16_HI = 16384;
+
+// The most zone segments a k_body launch may hold.  Segments wait on each other (zone_seg's
+// phase B), so all of them must be resident together: they are the launch's first blocks and
+// the 1024-thread form holds one workgroup per CU, which asks for nz <= CUs.  Above the 64
+// that every supported device has room for, the cap is half the CUs, so that the body keeps
+// at least as many workgroups as the zone (the 2 * extra <= body_cap rule of the grid).
+// `want`: GBPE_DEBUG zsmax (default NSEG_MAX).
+inline uint32_t zseg_cap(uint32_t num_cu, long want) {
+    const uint32_t room = std::max<uint32_t>(64u, num_cu / 2);
+    const uint32_t w = (uint32_t)std::min<long>(std::max<long>(want, 2), (long)NSEG_MAX);
+    return std::min(w, room);
+}
 
 template <typename S>
 uint32_t zone_max(int bt) {
@@ -375,6 +391,10 @@ void launch_body(int bt, uint32_t grid, hipStream_t s, A... args) {
         hipLaunchKernelGGL((k_body<S, EXACT, 1024, 16, true>), dim3(grid), dim3(1024), 0, s, args...);
     else if (bt == 2049)   // ... with 8K-symbol segments (zones <= 512K)
         hipLaunchKernelGGL((k_body<S, EXACT, 1024, 8, true>), dim3(grid), dim3(1024), 0, s, args...);
+    else if (bt == 2050) {   // ... with 32K-symbol segments (u16 zones of 2M-4M symbols)
+        if constexpr (sizeof(S) == 2)
+            hipLaunchKernelGGL((k_body<S, EXACT, 1024, 32, true>), dim3(grid), dim3(1024), 0, s, args...);
+    }
     else if (bt == 1023 && sizeof(S) == 2)
         hipLaunchKernelGGL((k_body<S, EXACT, 1024, 16>), dim3(grid), dim3(1024), 0, s, args...);
     else if (bt >= 1023)
@@ -393,7 +413,7 @@ int launch_merge_sparse(gbpe_trainer* t, uint32_t round, hipStream_t s, const Sp
     // zone segments run inside k_body (its ZSEG form)
     const bool inbody = g.zone1 >= 2;
     const uint32_t z1 = g.zone1;   // k_body's own zone workgroups
-    const int bt = inbody ? (g.seg8 ? 2049 : 2048) : g.bt;
+    const int bt = inbody ? (g.seg32 ? 2050 : g.seg8 ? 2049 : 2048) : g.bt;
     SelShard sh;
     sh.sub = g.sub;
     sh.k2 = g.pair ? 1u : 0u;
@@ -463,7 +483,7 @@ int launch_merge_sparse(gbpe_trainer* t, uint32_t round, hipStream_t s, const Sp
     }
     if (timing) TR_HIP(t, hipEventRecord(ev[2], s));
     GBPE_LAUNCH_REFRESH(S, g.refresh, t->tb.nblk, s, t->st.p, round, 2, t->tb, (S*)nullptr, (const uint32_t*)nullptr,
-                        t->zst.p, t->d_clog.p, FusedSel(), t->part.p, t->zseg.p);
+                        t->zst.p, t->d_clog.p, FusedSel(), t->part.p, t->zseg.p, inbody ? z1 : 0u);
     if (timing) TR_HIP(t, hipEventRecord(ev[4], s));
     GBPE_LAUNCH_CHECK(t->ctx);
     return GBPE_OK;
@@ -1231,6 +1251,8 @@ int trainer_config(gbpe_trainer* t, gbpe_ctx* ctx, const gbpe_train_opts* opts) 
     t->pair_on = gbpe_debug_knob("pair", 1) != 0;
     t->pair16_on = gbpe_debug_knob("pseg", 1) != 0;
     t->pair_prej = (uint32_t)std::max<long>(0, gbpe_debug_knob("prej", 0));
+    t->zseg_max = zseg_cap(t->body_cap, gbpe_debug_knob("zsmax", NSEG_MAX));
+    t->zseg32 = (uint32_t)gbpe_debug_knob("zs32", t->zseg32);
     t->ptrace = (uint32_t)gbpe_debug_knob("ptrace", 0);
     t->rehash_on = gbpe_debug_knob("rehash", 1) != 0;
     t->delta_mt = (uint32_t)gbpe_debug_knob("delta_mt", t->delta_mt);
