@@ -62,6 +62,9 @@ static const char* const kKernelNames[] = {
     // cl100k_base word starts (gbpe_pretokenize_cl100k*, GBPE_WORDS_CL100K)
     "k_pretok_cl100k",        // k_ptc_scan1 / k_ptc_scan2 / k_ptc_mark: the split pattern's rules + its three scans
     "k_pretok_cl100k_docs",   // k_ptc_scan1<true> / k_ptc_mark<true>: the same bounded by the document flags
+    // byte spans of the merge-rank encode's tokens (gbpe_bpe_encode_spans*)
+    "k_me_walk_spans",        // k_me_walk_spans<CS, SP, WIDE>: the document walk + each token's start beside it
+    "k_me_compact_spans",     // the compaction of the tokens and their starts
 };
 
 // ── context memory pool (common.h GbpePool) ───────────────────────────────

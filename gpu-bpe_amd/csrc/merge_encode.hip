@@ -37,9 +37,14 @@
 //          {a, b, rank, new id}, and a pair is keyed by 64 bits; the narrow form keeps a << 16 | b
 //          in one word.  merge_table.h builds either table on the host and holds the hash both
 //          sides share.  me_heap is the other reader of the slots and takes the same switch.
-// Two __global__ symbols carry it: k_me_walk<WORDS, CS, WIDE> (no DOCS, no SP) and
+//   SPANS  the byte span of every token: scratch holds {token, its start relative to
+//          the chunk's base} pairs; me_short_spans carries the pair through its compaction, me_heap
+//          writes a surviving node's index, a special's span its own start.
+// Three __global__ symbols carry it: k_me_walk<WORDS, CS, WIDE> (no DOCS, no SP),
 // k_me_walk_docs<CS, SP, WIDE> (WORDS and DOCS: a call with special tokens is launched as a batch
-// of no documents).  me_launch is the one place that picks an instantiation.
+// of no documents) and k_me_walk_spans<CS, SP, WIDE> (WORDS, DOCS and SPANS: a call without
+// documents or word starts runs under a mask of its own, zero for GBPE_WORDS_NONE).  me_launch is
+// the one place that picks an instantiation.
 //
 // The long-segment arena: a segment longer than ME_LONG bytes (CJK paragraphs, base64, minified
 // code: no cut for a long stretch) would cost its lane one full pass per rank applied; it is encoded
@@ -172,10 +177,12 @@ __global__ __launch_bounds__(ME_TPB) void k_me_long(const uint8_t* __restrict__ 
 // occurrences left to right, as the reference's one pass per merge does: a
 // merge's new pairs hold its new token, which only later ranks use.  Stale
 // entries (the pair at that position changed) are skipped on pop.
-template <bool WIDE>
+// SPANS: `out` is an array of uint2, {token, rel + the index of its node}: the node's index is its
+// token's first byte.
+template <bool WIDE, bool SPANS = false>
 __device__ uint32_t me_heap(const uint8_t* __restrict__ in, uint32_t len, const MeTable& t, uint32_t* __restrict__ tk,
                             uint32_t* __restrict__ nx, uint32_t* __restrict__ pv, uint64_t* __restrict__ hp,
-                            uint32_t* __restrict__ out) {
+                            uint32_t* __restrict__ out, uint32_t rel = 0) {
     for (uint32_t i = 0; i < len; ++i) {
         tk[i] = in[i];
         nx[i] = i + 1;
@@ -234,6 +241,11 @@ __device__ uint32_t me_heap(const uint8_t* __restrict__ in, uint32_t len, const 
         }
     }
     uint32_t cnt = 0;
+    if constexpr (SPANS) {
+        uint2* out2 = reinterpret_cast<uint2*>(out);
+        for (uint32_t i = 0; i < len; i = nx[i]) out2[cnt++] = make_uint2(tk[i], rel + i);
+        return cnt;
+    }
     for (uint32_t i = 0; i < len; i = nx[i]) out[cnt++] = tk[i];   // position 0 is never merged away
     return cnt;
 }
@@ -260,6 +272,35 @@ __device__ __forceinline__ uint32_t me_short(uint32_t* tok, uint32_t len, const 
             uint32_t v = tok[j++];
             if (j < len && me_pair<WIDE>(v, tok[j]) == bpid) {
                 v = bnew;
+                ++j;
+            }
+            tok[w++] = v;   // (w < j: behind what is still to be read)
+        }
+        len = w;
+    } while (len >= 2);
+    return len;
+}
+
+// me_short on {token, start} pairs (SPANS): the same two loops, and a token's start moves
+// with it — a merged pair keeps its left operand's.  One 8-byte element and not two arrays: the walk is
+// bound by its lanes' scattered loads and stores, and a pair costs the second loop no more of them.
+template <bool WIDE>
+__device__ __forceinline__ uint32_t me_short_spans(uint2* tok, uint32_t len, const MeTable& t) {
+    if (len >= 2) do {
+        uint32_t best = ME_NONE;
+        me_key_t<WIDE> bpid = 0;
+        uint32_t bnew = 0;
+        for (uint32_t j = 0; j + 1 < len; ++j) {
+            const me_key_t<WIDE> pid = me_pair<WIDE>(tok[j].x, tok[j + 1].x);
+            const uint4 e = me_find(t, pid);
+            if (e.y < best) { best = e.y; bpid = pid; bnew = e.z; }
+        }
+        if (best == ME_NONE) break;
+        uint32_t w = 0, j = 0;
+        while (j < len) {
+            uint2 v = tok[j++];
+            if (j < len && me_pair<WIDE>(v.x, tok[j].x) == bpid) {
+                v.x = bnew;
                 ++j;
             }
             tok[w++] = v;   // (w < j: behind what is still to be read)
@@ -299,8 +340,9 @@ struct MeSp {   // the special tokens of a call (SP)
 // start.  SP: a segment that begins with ME_SP_BIT is a special's span (its other bytes are no cut,
 // the byte after it is one): its id is the segment's one token.  It belongs to the chunk that holds
 // its first byte, and one token for at least one byte keeps the tokens of a chunk behind the bytes
-// it has consumed.
-template <bool WORDS, uint32_t CS, bool DOCS, bool SP, bool WIDE>
+// it has consumed.  SPANS: scratch is an array of uint2, and entry b0 + k is the chunk's k-th token
+// with its first byte, less b0.
+template <bool WORDS, uint32_t CS, bool DOCS, bool SP, bool WIDE, bool SPANS = false>
 __device__ __forceinline__ void me_walk(const uint8_t* __restrict__ in, const uint8_t* __restrict__ ws, uint64_t n,
                                         const MeTable& t, uint32_t* __restrict__ scratch, uint32_t* __restrict__ counts,
                                         uint64_t* __restrict__ base, uint64_t nchunks, const MeArena& ar,
@@ -322,13 +364,30 @@ __device__ __forceinline__ void me_walk(const uint8_t* __restrict__ in, const ui
             ws_s = ws_z;   // (z == n: not read, and the loop ends)
             if (w0 & ME_DOC_BIT) docs.written[me_first_doc(docs.doc_off, docs.n_docs, s)] = written;
             if (SP && (w0 & ME_SP_BIT)) {
-                scratch[b0 + written++] = sp.ids[sp.mark[s] - 1u];
+                if constexpr (SPANS)
+                    reinterpret_cast<uint2*>(scratch)[b0 + written++] = make_uint2(sp.ids[sp.mark[s] - 1u], (uint32_t)(s - b0));
+                else
+                    scratch[b0 + written++] = sp.ids[sp.mark[s] - 1u];
                 s = z;
                 continue;
             }
         }
         uint32_t* tok = scratch + b0 + written;
         const uint32_t len = (uint32_t)(z - s);
+        if constexpr (SPANS) {
+            uint2* tp = reinterpret_cast<uint2*>(scratch) + b0 + written;
+            const uint32_t rel = (uint32_t)(s - b0);   // (below CS: s and b0 lie in the chunk)
+            if (len > ME_LONG) {
+                const uint64_t off = ar.slot[c * me_lslot(CS) + nlong++];
+                written += me_heap<WIDE, true>(in + s, len, t, ar.tok + off, ar.nxt + off, ar.prv + off, ar.heap + 3 * off,
+                                               reinterpret_cast<uint32_t*>(tp), rel);
+            } else {
+                for (uint32_t j = 0; j < len; ++j) tp[j] = make_uint2(in[s + j], rel + j);
+                written += me_short_spans<WIDE>(tp, len, t);
+            }
+            s = z;
+            continue;
+        }
         if (len > ME_LONG) {
             const uint64_t off = ar.slot[c * me_lslot(CS) + nlong++];
             written += me_heap<WIDE>(in + s, len, t, ar.tok + off, ar.nxt + off, ar.prv + off, ar.heap + 3 * off, tok);
@@ -356,6 +415,15 @@ __global__ __launch_bounds__(ME_TPB) void k_me_walk_docs(const uint8_t* __restri
                                                          uint32_t* __restrict__ counts, uint64_t* __restrict__ base,
                                                          uint64_t nchunks, MeArena ar, MeDocs docs, MeSp sp) {
     me_walk<true, CS, true, SP, WIDE>(in, ws, n, t, scratch, counts, base, nchunks, ar, docs, sp);
+}
+
+// the spans form: the word and document walk on {token, start} pairs (scratch: n uint2)
+template <uint32_t CS, bool SP = false, bool WIDE = false>
+__global__ __launch_bounds__(ME_TPB) void k_me_walk_spans(const uint8_t* __restrict__ in, const uint8_t* __restrict__ ws,
+                                                          uint64_t n, MeTable t, uint32_t* __restrict__ scratch,
+                                                          uint32_t* __restrict__ counts, uint64_t* __restrict__ base,
+                                                          uint64_t nchunks, MeArena ar, MeDocs docs, MeSp sp) {
+    me_walk<true, CS, true, SP, WIDE, true>(in, ws, n, t, scratch, counts, base, nchunks, ar, docs, sp);
 }
 
 // the caller's mask as 0 / 1 (any alignment), four bytes per lane: bit 1 stays free for the document starts
@@ -445,6 +513,30 @@ __global__ __launch_bounds__(256) void k_me_compact(const uint32_t* __restrict__
     }
 }
 
+// the spans form: scratch holds {token, relative start}; tok_start[d] = the chunk's base + the start, beside out[d]
+__global__ __launch_bounds__(256) void k_me_compact_spans(const uint2* __restrict__ scratch,
+                                                          const uint32_t* __restrict__ counts,
+                                                          const uint64_t* __restrict__ base,
+                                                          const uint32_t* __restrict__ local,
+                                                          const uint64_t* __restrict__ blocksum, uint64_t nchunks,
+                                                          uint32_t* __restrict__ out, uint64_t* __restrict__ tok_start,
+                                                          uint64_t out_cap) {
+    const uint64_t chunk = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (chunk >= nchunks) return;
+    const int lane = threadIdx.x & 63;
+    const uint64_t off = blocksum[chunk / SCAN_BLK] + local[chunk];
+    const uint32_t cnt = counts[chunk];
+    const uint64_t b0 = base[chunk];
+    for (uint32_t j = lane; j < cnt; j += 64) {
+        const uint64_t d = off + j;
+        if (d < out_cap) {
+            const uint2 v = scratch[b0 + j];
+            out[d] = v.x;
+            tok_start[d] = b0 + v.y;
+        }
+    }
+}
+
 }  // namespace
 
 struct gbpe_bpe {
@@ -518,7 +610,7 @@ namespace {
 inline uint64_t up16(uint64_t x) { return (x + 15) & ~15ull; }
 
 struct MeWork {   // the device arrays of one call, each 16-byte aligned inside one pooled block
-    uint32_t* scratch;    // n: a chunk's tokens from its first segment start (<= 1 per byte)
+    uint32_t* scratch;    // n: a chunk's tokens from its first segment start (<= 1 per byte); spans: n uint2
     uint32_t* counts;     // nchunks
     uint64_t* base;       // nchunks
     uint32_t* local;      // nchunks
@@ -533,11 +625,17 @@ struct MeWork {   // the device arrays of one call, each 16-byte aligned inside 
     // special tokens only
     uint8_t* mark;           // n: gbpe_specials_mark's array
     uint8_t* cand;           // n
+    // a spans call: scratch holds uint2 {token, start}, entry base[c] + k being chunk c's k-th
+    // token and its first byte less base[c].  A token starts inside a segment that starts in the chunk, so
+    // the start is below CS + the chunk's longest segment.  The walk holds a segment's length in 32 bits;
+    // the entry points keep n at most ME_SPANS_MAX_N = 2^32 - 1 - 4096, so the sum cannot wrap a u32 either.
+    bool spans;
 };
+constexpr uint64_t ME_SPANS_MAX_N = 0xFFFFFFFFull - 4096u;
 
 hipError_t me_layout(gbpe_ctx* ctx, GbpeArray<uint8_t>& blk, uint64_t n, uint32_t cs, uint64_t nchunks, uint64_t nblk,
-                     uint64_t n_docs, bool flags, bool special, MeWork* w) {
-    const uint64_t o_counts = up16(4 * n), o_base = o_counts + up16(4 * nchunks), o_local = o_base + up16(8 * nchunks);
+                     uint64_t n_docs, bool flags, bool special, bool spans, MeWork* w) {
+    const uint64_t o_counts = up16((spans ? 8 : 4) * n), o_base = o_counts + up16(4 * nchunks), o_local = o_base + up16(8 * nchunks);
     const uint64_t o_bsum = o_local + up16(4 * nchunks), o_slot = o_bsum + up16(8 * (nblk + 2));
     const uint64_t o_back = o_slot + up16(8 * nchunks * me_lslot(cs)), o_docw = o_back + 16;
     const uint64_t o_mask = o_docw + up16(4 * n_docs), o_flags = o_mask + up16(n), o_mark = o_flags + (flags ? up16(n) : 0);
@@ -547,7 +645,7 @@ hipError_t me_layout(gbpe_ctx* ctx, GbpeArray<uint8_t>& blk, uint64_t n, uint32_
     uint8_t* p = blk.p;
     *w = MeWork{(uint32_t*)p, (uint32_t*)(p + o_counts), (uint64_t*)(p + o_base), (uint32_t*)(p + o_local),
                 (uint64_t*)(p + o_bsum), (uint64_t*)(p + o_bsum) + nblk + 1, (uint64_t*)(p + o_slot),
-                (unsigned long long*)(p + o_back), nullptr, nullptr, nullptr, nullptr, nullptr};
+                (unsigned long long*)(p + o_back), nullptr, nullptr, nullptr, nullptr, nullptr, spans};
     if (n_docs || special) w->doc_written = (uint32_t*)(p + o_docw), w->mask = p + o_mask;
     if (flags) w->flags = p + o_flags;
     if (special) w->mark = p + o_mark, w->cand = p + o_mark + up16(n);
@@ -572,7 +670,8 @@ hipError_t me_arena(gbpe_ctx* ctx, GbpeArray<uint8_t>& blk, uint64_t long_total,
 // total sizes it) k_me_long, with special tokens under the SP predicate, the cuts of the SP walk.
 // With one, the walk: k_me_walk; with the documents of a batch call (always the word form)
 // k_me_walk_docs; with special tokens its SP form, for one buffer too (no document bit is set then:
-// `docs` is not read).  `wide`: the layout of t's slots, gbpe_bpe::wide.
+// `docs` is not read).  `wide`: the layout of t's slots, gbpe_bpe::wide.  A spans call (w.spans) walks
+// with k_me_walk_spans, the document form whatever the call holds, SP with special tokens.
 template <bool WORDS, uint32_t CS>
 void me_launch(hipStream_t s, const uint8_t* in, const uint8_t* ws, uint64_t n, const MeTable& t, bool wide,
                const MeWork& w, uint64_t nchunks, const MeArena* ar, const MeDocs* docs, const MeSp* sp) {
@@ -590,6 +689,15 @@ void me_launch(hipStream_t s, const uint8_t* in, const uint8_t* ws, uint64_t n, 
     auto walk = [&](auto wide_c) {
         constexpr bool WIDE = decltype(wide_c)::value;
         if constexpr (WORDS) {
+            if (w.spans) {
+                if (sp)
+                    hipLaunchKernelGGL((k_me_walk_spans<CS, true, WIDE>), grid, tpb, 0, s, in, ws, n, t, w.scratch, w.counts,
+                                       w.base, nchunks, *ar, docs ? *docs : MeDocs{}, *sp);
+                else
+                    hipLaunchKernelGGL((k_me_walk_spans<CS, false, WIDE>), grid, tpb, 0, s, in, ws, n, t, w.scratch, w.counts,
+                                       w.base, nchunks, *ar, docs ? *docs : MeDocs{}, MeSp{});
+                return;
+            }
             if (sp) {
                 hipLaunchKernelGGL((k_me_walk_docs<CS, true, WIDE>), grid, tpb, 0, s, in, ws, n, t, w.scratch, w.counts,
                                    w.base, nchunks, *ar, docs ? *docs : MeDocs{}, *sp);
@@ -667,11 +775,13 @@ int me_mask(gbpe_ctx* ctx, const uint8_t* d_in, uint64_t n, const uint8_t* d_ws,
 // With `docs`, also d_doc_off[0, n_docs] → d_tok_off[0, n_docs]: the tokens are the word kernels'
 // under me_mask's mask; with `sp` (special tokens), of the pieces between the accepted specials.  The offsets' verdict comes back with the long-segment total, the
 // call's first synchronise, before anything is written to d_out or d_tok_off.  `what` names the
-// entry point in error texts.
+// entry point in error texts.  `spans`: also d_tok_start[0, min(total, out_cap)), each token's first
+// byte; the call runs the word and document form under a 0 / 1 mask of its own.
 int me_run(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, const char* what, const uint8_t* d_in, uint64_t n,
-           const uint8_t* d_ws, uint32_t mode, uint32_t* d_out, uint64_t out_cap, const MeDocJob* docs, uint64_t* n_out) {
+           const uint8_t* d_ws, uint32_t mode, uint32_t* d_out, uint64_t out_cap, const MeDocJob* docs, uint64_t* n_out,
+           bool spans = false, uint64_t* d_tok_start = nullptr) {
     hipStream_t s = ctx->stream;
-    const bool words = docs || sp || mode != GBPE_WORDS_NONE;   // (a document start, a special's edge is a cut)
+    const bool words = spans || docs || sp || mode != GBPE_WORDS_NONE;   // (a document start, a special's edge is a cut)
     uint32_t cs = ME_CS;
     if (words) {
         cs = (uint32_t)gbpe_debug_knob("me_cs", ME_CS_WORDS);   // (read per call: the bench and the tests run all three)
@@ -684,7 +794,7 @@ int me_run(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, const char* wha
     MeWork w;
     // (flags: the pre-tokenisers' piece starts; the document starts the matcher must not cross)
     GBPE_HIP(ctx, me_layout(ctx, work, n, cs, nchunks, nblk, docs ? docs->n_docs : 0,
-                            (docs || sp) && (me_pretok(mode) || (docs && sp)), sp != nullptr, &w));
+                            (docs || sp) && (me_pretok(mode) || (docs && sp)), sp != nullptr, spans, &w));
     const MeTable t{bp->slots, bp->mask, bp->cross};
     const uint64_t cell = docs ? 16 : 8;   // of w.back: a batch call also reads the offsets' verdict
 
@@ -694,6 +804,12 @@ int me_run(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, const char* wha
         GBPE_HIP(ctx, hipMemsetAsync(w.back, 0, cell, s));
         rc = me_mask(ctx, d_in, n, d_ws, mode, docs, sp, w);
         d_ws = w.mask;
+    } else if (spans && (mode == GBPE_WORDS_NONE || mode == GBPE_WORDS_MASK)) {
+        // the document walk reads the mask's bits: nothing for NONE, the caller's as 0 / 1
+        GBPE_HIP(ctx, mask.reserve(ctx, n));
+        if (mode == GBPE_WORDS_NONE) GBPE_HIP(ctx, hipMemsetAsync(mask.p, 0, n, s));
+        else hipLaunchKernelGGL(k_me_mask01, dim3((uint32_t)gbpe_div_up(n, 1024)), dim3(256), 0, s, d_ws, n, mask.p);
+        d_ws = mask.p;
     } else if (mode == GBPE_WORDS_HEURISTIC || me_pretok(mode)) {
         GBPE_HIP(ctx, mask.reserve(ctx, n));
         rc = mode == GBPE_WORDS_GPT4     ? gbpe_pretok_gpt4_launch(ctx, d_in, n, mask.p)
@@ -735,7 +851,12 @@ int me_run(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, const char* wha
         hipLaunchKernelGGL(k_chunk_scan1, dim3((uint32_t)nblk), dim3(SCAN_TPB), 0, s, (const uint32_t*)w.counts, nchunks,
                            w.local, w.blocksum);
         hipLaunchKernelGGL(k_chunk_scan2, dim3(1), dim3(SCAN_TPB), 0, s, w.blocksum, nblk, w.total);
-        if (out_cap)
+        if (out_cap && spans)
+            hipLaunchKernelGGL(k_me_compact_spans, dim3((uint32_t)gbpe_div_up(nchunks, 4)), dim3(256), 0, s,
+                               (const uint2*)w.scratch, (const uint32_t*)w.counts,
+                               (const uint64_t*)w.base, (const uint32_t*)w.local, (const uint64_t*)w.blocksum, nchunks,
+                               d_out, d_tok_start, out_cap);
+        else if (out_cap)
             hipLaunchKernelGGL(k_me_compact, dim3((uint32_t)gbpe_div_up(nchunks, 4)), dim3(256), 0, s,
                                (const uint32_t*)w.scratch, (const uint32_t*)w.counts, (const uint64_t*)w.base,
                                (const uint32_t*)w.local, (const uint64_t*)w.blocksum, nchunks, d_out, out_cap);
@@ -806,10 +927,12 @@ int me_check(gbpe_ctx* ctx, const gbpe_bpe* bp, const gbpe_specials* sp, bool sp
 
 int me_device(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, bool special, bool batch, const void* d_bytes,
               uint64_t n, const void* d_doc_off, uint64_t n_docs, const void* d_word_starts, uint32_t words_mode,
-              void* d_out, uint64_t out_cap, void* d_tok_off, uint64_t* n_out) {
+              void* d_out, uint64_t out_cap, void* d_tok_off, uint64_t* n_out, bool spans = false,
+              void* d_tok_start = nullptr) {
     const int rc = me_check(ctx, bp, sp, special, batch, true, d_bytes, n, d_doc_off, n_docs, d_word_starts, words_mode,
                             d_out, out_cap, d_tok_off, n_out);
     if (rc != GBPE_OK) return rc;
+    if (spans && ((uintptr_t)d_tok_start & 7u)) return gbpe_set_error(ctx, GBPE_E_INVALID, "d_tok_start must be 8-byte aligned");
     if (n == 0 || (batch && n_docs == 0)) {
         if (batch) {
             GBPE_HIP(ctx, hipMemsetAsync(d_tok_off, 0, (n_docs + 1) * 8, ctx->stream));
@@ -819,14 +942,14 @@ int me_device(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, bool special
     }
     const MeDocJob docs{(const uint64_t*)d_doc_off, n_docs, (uint64_t*)d_tok_off};
     return me_run(ctx, bp, sp, batch ? "bpe encode batch" : "bpe encode (words)", (const uint8_t*)d_bytes, n, (const uint8_t*)d_word_starts, words_mode,
-                  (uint32_t*)d_out, out_cap, batch ? &docs : nullptr, n_out);
+                  (uint32_t*)d_out, out_cap, batch ? &docs : nullptr, n_out, spans, (uint64_t*)d_tok_start);
 }
 
 // Host buffers: one upload of the offsets (a batch call), the bytes (and the mask), me_run, and back
 // come the token offsets (a batch call) and the tokens that fit: at most one per byte.
 int me_host(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, bool special, bool batch, const uint8_t* bytes, uint64_t n,
             const uint64_t* doc_off, uint64_t n_docs, const uint8_t* word_starts, uint32_t words_mode, uint32_t* out,
-            uint64_t out_cap, uint64_t* tok_off, uint64_t* n_out) {
+            uint64_t out_cap, uint64_t* tok_off, uint64_t* n_out, bool spans = false, uint64_t* tok_start = nullptr) {
     int rc = me_check(ctx, bp, sp, special, batch, false, bytes, n, doc_off, n_docs, word_starts, words_mode, out, out_cap,
                       tok_off, n_out);
     if (rc != GBPE_OK) return rc;
@@ -843,9 +966,9 @@ int me_host(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, bool special, 
     const uint64_t cap = out_cap < n ? out_cap : n;
     const uint64_t off_bytes = batch ? 8 * (n_docs + 1) : 0;
     const uint64_t o_tok = up16(off_bytes), o_in = 2 * o_tok, o_ws = o_in + up16(n);
-    const uint64_t o_out = o_ws + (word_starts ? up16(n) : 0);
+    const uint64_t o_out = o_ws + (word_starts ? up16(n) : 0), o_ts = o_out + up16(4 * cap);   // (spans: the starts)
     GbpeArray<uint8_t> io;
-    GBPE_HIP(ctx, io.reserve(ctx, o_out + 4 * cap + 16));
+    GBPE_HIP(ctx, io.reserve(ctx, (spans ? o_ts + 8 * cap : o_out + 4 * cap) + 16));
     hipStream_t s = ctx->stream;
     uint8_t* d_ws = word_starts ? io.p + o_ws : nullptr;
     hipError_t e = batch ? hipMemcpyAsync(io.p, doc_off, off_bytes, hipMemcpyHostToDevice, s) : hipSuccess;
@@ -854,11 +977,12 @@ int me_host(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, bool special, 
     if (e == hipSuccess) {
         const MeDocJob docs{(const uint64_t*)io.p, n_docs, (uint64_t*)(io.p + o_tok)};
         rc = me_run(ctx, bp, sp, what, io.p + o_in, n, d_ws, words_mode, (uint32_t*)(io.p + o_out), cap,
-                    batch ? &docs : nullptr, n_out);
+                    batch ? &docs : nullptr, n_out, spans, (uint64_t*)(io.p + o_ts));
         if (rc != GBPE_OK && rc != GBPE_E_CAPACITY) return rc;   // (synchronised there)
         if (batch) e = hipMemcpyAsync(tok_off, io.p + o_tok, off_bytes, hipMemcpyDeviceToHost, s);
         const uint64_t fit = *n_out < cap ? *n_out : cap;
         if (e == hipSuccess && fit) e = hipMemcpyAsync(out, io.p + o_out, fit * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && fit && spans) e = hipMemcpyAsync(tok_start, io.p + o_ts, fit * 8, hipMemcpyDeviceToHost, s);
     }
     const hipError_t es = hipStreamSynchronize(s);
     if (e == hipSuccess) e = es;
@@ -866,7 +990,43 @@ int me_host(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, bool special, 
     return rc;
 }
 
+// What the spans calls check before me_check: the call's shape is read off its pointers —
+// documents when doc_off is given, a special table when `specials` is — and n stays where a token's
+// relative start fits a u32 (MeWork::spans).
+int me_spans_check(gbpe_ctx* ctx, uint64_t n, const void* doc_off, uint64_t n_docs, const void* tok_start, uint64_t out_cap,
+                   const void* tok_off, uint64_t* n_out) {
+    if (n_out) *n_out = 0;
+    if ((doc_off != nullptr) != (tok_off != nullptr))
+        return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe encode (spans): doc_off and tok_off go together");
+    if (!doc_off && n_docs) return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe encode (spans): n_docs without doc_off");
+    if (out_cap && !tok_start) return gbpe_set_error(ctx, GBPE_E_INVALID, "null argument");
+    if (n > ME_SPANS_MAX_N)
+        return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe encode (spans): %llu bytes, above the limit of %llu",
+                              (unsigned long long)n, (unsigned long long)ME_SPANS_MAX_N);
+    return GBPE_OK;
+}
+
 }  // namespace
+
+extern "C" int gbpe_bpe_encode_spans(gbpe_ctx* ctx, gbpe_bpe* bp, gbpe_specials* sp, const uint8_t* bytes, uint64_t n,
+                                     const uint64_t* doc_off, uint64_t n_docs, const uint8_t* word_starts,
+                                     uint32_t words_mode, uint32_t* out, uint64_t* tok_start, uint64_t out_cap,
+                                     uint64_t* tok_off, uint64_t* n_out) {
+    const int rc = me_spans_check(ctx, n, doc_off, n_docs, tok_start, out_cap, tok_off, n_out);
+    if (rc != GBPE_OK) return rc;
+    return me_host(ctx, bp, sp, sp != nullptr, doc_off != nullptr, bytes, n, doc_off, n_docs, word_starts, words_mode, out,
+                   out_cap, tok_off, n_out, true, tok_start);
+}
+
+extern "C" int gbpe_bpe_encode_spans_device(gbpe_ctx* ctx, gbpe_bpe* bp, gbpe_specials* sp, const void* d_bytes, uint64_t n,
+                                            const void* d_doc_off, uint64_t n_docs, const void* d_word_starts,
+                                            uint32_t words_mode, void* d_out, void* d_tok_start, uint64_t out_cap,
+                                            void* d_tok_off, uint64_t* n_out) {
+    const int rc = me_spans_check(ctx, n, d_doc_off, n_docs, d_tok_start, out_cap, d_tok_off, n_out);
+    if (rc != GBPE_OK) return rc;
+    return me_device(ctx, bp, sp, sp != nullptr, d_doc_off != nullptr, d_bytes, n, d_doc_off, n_docs, d_word_starts,
+                     words_mode, d_out, out_cap, d_tok_off, n_out, true, d_tok_start);
+}
 
 extern "C" int gbpe_bpe_encode_words_device(gbpe_ctx* ctx, gbpe_bpe* bp, const void* d_bytes, uint64_t n,
                                             const void* d_word_starts, uint32_t words_mode, void* d_out, uint64_t out_cap,

@@ -137,6 +137,11 @@ _SIGS = [
     ("gbpe_bpe_encode_special_batch_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                                        C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
                                                        C.c_uint64, C.c_void_p, u64p]),
+    ("gbpe_bpe_encode_spans", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_uint64,
+                                        C.c_void_p, C.c_uint32, u32p, u64p, C.c_uint64, u64p, u64p]),
+    ("gbpe_bpe_encode_spans_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                               C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                               C.c_void_p, u64p]),
     ("gbpe_encode_last_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                           C.POINTER(C.c_double)]),
     ("gbpe_vocab_upload", C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_uint32, C.POINTER(C.c_void_p)]),

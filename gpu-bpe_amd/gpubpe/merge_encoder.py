@@ -215,6 +215,50 @@ class MergeEncoder:
             _lib.check(lib.gbpe_bpe_encode_words_batch(ctx, self._h, *args), ctx, "bpe encode batch")
         return out[: cnt.value].copy(), tok_off
 
+    def _spans(self, buf, n, offs, n_docs, mode, mask, sp):
+        """gbpe_bpe_encode_spans over np.uint8 ``buf``: (tokens, tok_off or None, starts with n appended)."""
+        lib = _lib.load()
+        ctx = self._engine.device
+        out = np.empty(max(1, n), dtype=np.uint32)
+        starts = np.empty(max(1, n) + 1, dtype=np.uint64)
+        tok_off = np.zeros(n_docs + 1, dtype=np.uint64) if offs is not None else None
+        cnt = C.c_uint64()
+        if mask is not None and not n:
+            mask = np.zeros(1, dtype=np.uint8)   # (a non-NULL pointer goes with the mode)
+        _lib.check(lib.gbpe_bpe_encode_spans(ctx, self._h, sp, buf.ctypes.data_as(C.c_void_p) if n else None, n,
+                                             offs.ctypes.data_as(_lib.u64p) if offs is not None else None, n_docs,
+                                             mask.ctypes.data_as(C.c_void_p) if mask is not None else None, mode,
+                                             out.ctypes.data_as(_lib.u32p), starts.ctypes.data_as(_lib.u64p), out.shape[0],
+                                             tok_off.ctypes.data_as(_lib.u64p) if offs is not None else None,
+                                             C.byref(cnt)), ctx, "bpe encode (spans)")
+        k = int(cnt.value)
+        starts[k] = n
+        return out[:k].copy(), tok_off, starts[: k + 1].copy()
+
+    def encode_bytes_spans(self, data, word_starts=None, words=None, special=None):
+        """``encode_bytes`` with the byte span of every token (gbpe_bpe_encode_spans):
+        returns ``(tokens, starts)``.  ``starts`` is np.uint64[len(tokens) + 1], the
+        index of each token's first byte and ``len(data)`` at the end, so
+        ``data[starts[i]:starts[i + 1]]`` are token i's bytes; a special's token covers
+        the special's bytes.  Arguments and checks are ``encode_bytes``'s."""
+        data = bytes(data)
+        mode, mask = checked_word_starts(len(data), word_starts, words)
+        sp = self._special(special)
+        tokens, _, starts = self._spans(np.frombuffer(data, dtype=np.uint8), len(data), None, 0, mode, mask, sp)
+        return tokens, starts
+
+    def encode_batch_spans(self, docs, offsets=None, word_starts=None, words=None, special=None):
+        """``encode_batch`` with the byte span of every token: returns
+        ``(tokens, offsets, starts)``; ``starts`` as in ``encode_bytes_spans``, counted
+        in the concatenation of the documents.  A non-empty document d's first token
+        starts at its first byte: ``starts[offsets[d]]`` is its byte offset."""
+        from .tokenizer import flatten_documents
+        buf, offs = flatten_documents(docs, offsets)
+        n, n_docs = int(buf.shape[0]), int(offs.shape[0]) - 1
+        mode, mask = checked_word_starts(n, word_starts, words)
+        sp = self._special(special)
+        return self._spans(buf, n, offs, n_docs, mode, mask, sp)
+
     def encode(self, text, word_starts=None, words=None, special=None) -> dict:
         """{tokens, text} like TokenizerManager.encode's result (tokenizer-manager.js:60)."""
         data = text.encode("utf-8") if isinstance(text, str) else bytes(text)

@@ -719,6 +719,65 @@ napi_value bpe_encode_words_batch(napi_env env, napi_callback_info info, bool sp
 napi_value BpeEncodeWordsBatch(napi_env env, napi_callback_info info) { return bpe_encode_words_batch(env, info, false); }
 napi_value BpeEncodeSpecialBatch(napi_env env, napi_callback_info info) { return bpe_encode_words_batch(env, info, true); }
 
+// bpeEncodeSpans(ctx, bpe, specials | null, bytes, offsets | null, wordStarts | null, mode) ->
+// { tokens, starts[, offsets] }: gbpe_bpe_encode_spans, the most general encode call with the first byte of
+// every token.  starts is a Float64Array of tokens.length + 1 entries, the input's length at the end;
+// offsets (the documents' token offsets) is there when offsets were given.
+napi_value BpeEncodeSpans(napi_env env, napi_callback_info info) {
+    size_t argc = 7;
+    napi_value argv[7];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Ctx* c = argc >= 1 ? unwrap_external<Ctx>(env, argv[0]) : nullptr;
+    Bpe* b = argc >= 2 ? unwrap_external<Bpe>(env, argv[1]) : nullptr;
+    const uint8_t *data = nullptr, *ws = nullptr;
+    size_t len = 0, ws_len = 0;
+    uint32_t mode = 0;
+    std::vector<uint64_t> doc_off;
+    Specials* sp = nullptr;
+    bool has_sp = false, has_off = false, has_ws = false;
+    bool ok = ctx_usable(c) && b && b->bpe && argc >= 7 && get_bytes(env, argv[3], &data, &len) &&
+              napi_get_value_uint32(env, argv[6], &mode) == napi_ok;
+    auto given = [&](napi_value v, bool* has) {
+        napi_valuetype vt;
+        if (napi_typeof(env, v, &vt) != napi_ok) return false;
+        *has = vt != napi_null && vt != napi_undefined;
+        return true;
+    };
+    if (ok) ok = given(argv[2], &has_sp) && given(argv[4], &has_off) && given(argv[5], &has_ws);
+    if (ok && has_sp) {
+        sp = unwrap_external<Specials>(env, argv[2]);
+        ok = sp && sp->sp;
+    }
+    if (ok && has_off) ok = get_doc_offsets(env, argv[4], &doc_off);
+    if (ok && has_ws) ok = get_bytes(env, argv[5], &ws, &ws_len) && ws_len == len;
+    if (!ok) {
+        napi_throw_type_error(env, nullptr,
+                              "bpeEncodeSpans(ctx, bpe, specials | null, Uint8Array, offsets: Float64Array of non-negative "
+                              "integers | null, wordStarts: Uint8Array of the same length | null, mode)");
+        return nullptr;
+    }
+    static const uint8_t kNoByte = 0;
+    if (has_ws && !ws) ws = &kNoByte;   // (an empty mask still goes with mode 1)
+    std::vector<uint32_t> out(len ? len : 1);
+    std::vector<uint64_t> starts(out.size() + 1);
+    std::vector<uint64_t> tok_off(doc_off.size(), 0);
+    uint64_t n = 0;
+    std::unique_lock<std::mutex> g(c->mu);
+    int rc = gbpe_bpe_encode_spans(c->ctx, b->bpe, has_sp ? sp->sp : nullptr, data, len, has_off ? doc_off.data() : nullptr,
+                                   has_off ? doc_off.size() - 1 : 0, has_ws ? ws : nullptr, mode, out.data(), starts.data(),
+                                   out.size(), has_off ? tok_off.data() : nullptr, &n);
+    g.unlock();
+    if (rc != GBPE_OK) return throw_status(env, c->ctx, "bpe encode (spans)", rc);
+    starts.resize((size_t)n + 1);
+    starts[(size_t)n] = len;
+    napi_value obj;
+    NAPI_CALL(env, napi_create_object(env, &obj));
+    NAPI_CALL(env, napi_set_named_property(env, obj, "tokens", make_u32_array(env, out.data(), (size_t)n)));
+    NAPI_CALL(env, napi_set_named_property(env, obj, "starts", make_f64_array(env, starts)));
+    if (has_off) NAPI_CALL(env, napi_set_named_property(env, obj, "offsets", make_f64_array(env, tok_off)));
+    return obj;
+}
+
 // specialsUpload(ctx, bytes: Uint8Array, offsets: Float64Array, ids: Uint32Array) -> external: special i is
 // bytes[offsets[i], offsets[i + 1]) with id ids[i] (gbpe_specials_upload)
 napi_value SpecialsUpload(napi_env env, napi_callback_info info) {
@@ -1225,6 +1284,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"specialsMark", nullptr, SpecialsMark, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"bpeEncodeSpecial", nullptr, BpeEncodeSpecial, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"bpeEncodeSpecialBatch", nullptr, BpeEncodeSpecialBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"bpeEncodeSpans", nullptr, BpeEncodeSpans, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"pretokenizeGpt4Batch", nullptr, PretokenizeGpt4Batch, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"pretokenizeCl100k", nullptr, PretokenizeCl100k, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"pretokenizeCl100kBatch", nullptr, PretokenizeCl100kBatch, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -12,6 +12,9 @@
  * matches those strings on the raw bytes: each is one token and the text between
  * them is encoded as if alone; opts.special === false gives the result without the
  * table, findSpecial(bytes, offsets) the matches (0 / 1 + index / 255 per byte).
+ * encodeBytesSpans / encodeBatchSpans take the same opts and also return starts, a
+ * Float64Array of tokens.length + 1 byte offsets (the input's length at the end): token i
+ * covers bytes starts[i] to starts[i + 1], a special's token the special's bytes.
  * Exact for every merge list whose new ids are at least 256 and distinct (any order,
  * repeated pairs, the pair (0, 0) and operands created later or never included); a
  * new id below 256 or given twice makes the constructor throw (GBPE_E_INVALID, the
@@ -160,6 +163,45 @@ export class MergeEncoder {
             return native().bpeEncodeSpecialBatch(this._engine.device, this._h, sp, flat.bytes, flat.offsets, ws, mode);
         }
         return native().bpeEncodeWordsBatch(this._engine.device, this._h, flat.bytes, flat.offsets, ws, mode);
+    }
+
+    /** The mode and mask of opts, checked as encodeBytes / encodeBatch check them; `name` is the caller's. */
+    _wordsOf(name, n, opts) {
+        const ws = opts && opts.wordStarts !== undefined && opts.wordStarts !== null ? opts.wordStarts : null;
+        const words = opts && opts.words !== undefined && opts.words !== null ? opts.words : null;
+        if (ws !== null && words !== null) throw new TypeError(name + ': give wordStarts or words, not both');
+        if (ws !== null) {
+            if (!(ws instanceof Uint8Array) || ws.length !== n) {
+                throw new TypeError(name + ': wordStarts must be a Uint8Array with one entry per byte');
+            }
+            return { mask: ws, mode: WORDS_MASK };
+        }
+        if (words === null) return { mask: null, mode: 0 };
+        if (!Object.prototype.hasOwnProperty.call(WORDS_MODES, words)) {
+            throw new TypeError(name + ": words must be 'gpt4', 'heuristic' or 'cl100k'");
+        }
+        return { mask: null, mode: WORDS_MODES[words] };
+    }
+
+    /**
+     * encodeBytes with the byte span of every token (gbpe_bpe_encode_spans):
+     * { tokens: Uint32Array, starts: Float64Array }, starts[i] the first byte of token i
+     * and bytes.length at the end.  Options and errors are encodeBytes's.
+     */
+    encodeBytesSpans(bytes, opts) {
+        const w = this._wordsOf('encodeBytes', bytes.length, opts);
+        return native().bpeEncodeSpans(this._engine.device, this._h, this._special(opts), bytes, null, w.mask, w.mode);
+    }
+
+    /**
+     * encodeBatch with the byte span of every token: { tokens, offsets, starts }, starts
+     * counted in the concatenation of the documents.  Options and errors are encodeBatch's.
+     */
+    encodeBatchSpans(docs, opts) {
+        const flat = flattenDocuments(docs, opts && opts.offsets);
+        const w = this._wordsOf('encodeBatch', flat.bytes.length, opts);
+        return native().bpeEncodeSpans(this._engine.device, this._h, this._special(opts), flat.bytes, flat.offsets, w.mask,
+            w.mode);
     }
 
     async encode(text, opts) {

@@ -542,6 +542,36 @@ int gbpe_bpe_encode_special_batch_device(gbpe_ctx* ctx, gbpe_bpe* bpe, gbpe_spec
                                          uint32_t words_mode, void* d_out, uint64_t out_cap, void* d_tok_off,
                                          uint64_t* n_out);
 
+/* ── byte spans of the merge-rank encode's tokens ─────────────
+ * The most general encode call, with the first byte of every token beside its id.
+ * The call's shape is read off its arguments: specials == NULL applies no special
+ * table; doc_off == NULL with n_docs == 0 is one document, and tok_off is NULL
+ * exactly when doc_off is (anything else: GBPE_E_INVALID).  out is bit for bit what
+ * gbpe_bpe_encode_words, _words_batch, _special or _special_batch gives for the same
+ * arguments.  tok_start[i] is the index in bytes of the first byte of token i, counted
+ * in the whole concatenation for a batch call; token i covers
+ * [tok_start[i], tok_start[i+1]) and the last token ends at n.  The tokens tile the
+ * input, so no closing entry is written; an empty document contributes no token; a
+ * special's one token covers exactly the special's bytes, whatever its id.
+ * On GBPE_E_CAPACITY *n_out holds the required count, the first out_cap entries of
+ * both out and tok_start are in place, nothing is written at or beyond index out_cap
+ * of either, and tok_off is complete.  out == NULL and tok_start == NULL go with
+ * out_cap == 0 only (the size query).  n == 0, bad offsets, the mode and mask rules
+ * are those of the calls of the same shape.  n above 2^32 - 1 - 4096 is
+ * GBPE_E_INVALID with nothing launched: a token's start is kept relative to its
+ * chunk in 32 bits.  gbpe_bpe_encode_last_timing reports these calls too. */
+int gbpe_bpe_encode_spans(gbpe_ctx* ctx, gbpe_bpe* bpe, gbpe_specials* specials, const uint8_t* bytes, uint64_t n,
+                          const uint64_t* doc_off, uint64_t n_docs, const uint8_t* word_starts, uint32_t words_mode,
+                          uint32_t* out, uint64_t* tok_start, uint64_t out_cap, uint64_t* tok_off, uint64_t* n_out);
+/* Device-resident variant, on the context's stream: d_tok_start, d_doc_off and
+ * d_tok_off (u64) are 8-byte aligned and d_out (u32) 4-byte aligned, else
+ * GBPE_E_INVALID with nothing launched; d_bytes and d_word_starts may have any
+ * alignment.  Only d_out and d_tok_start[0, min(total, out_cap)) and
+ * d_tok_off[0, n_docs] are written. */
+int gbpe_bpe_encode_spans_device(gbpe_ctx* ctx, gbpe_bpe* bpe, gbpe_specials* specials, const void* d_bytes, uint64_t n,
+                                 const void* d_doc_off, uint64_t n_docs, const void* d_word_starts, uint32_t words_mode,
+                                 void* d_out, void* d_tok_start, uint64_t out_cap, void* d_tok_off, uint64_t* n_out);
+
 /* device ms of the last encode's kernels (walk, scan, compact); after a batch call:
  * the walk, every scan and table kernel (document table, descriptors, count scan),
  * the compaction with the document token offsets (the last group's, when the host
