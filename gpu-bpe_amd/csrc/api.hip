@@ -65,6 +65,9 @@ static const char* const kKernelNames[] = {
     // byte spans of the merge-rank encode's tokens (gbpe_bpe_encode_spans*)
     "k_me_walk_spans",        // k_me_walk_spans<CS, SP, WIDE>: the document walk + each token's start beside it
     "k_me_compact_spans",     // the compaction of the tokens and their starts
+    // o200k_base word starts (gbpe_pretokenize_o200k*, GBPE_WORDS_O200K)
+    "k_pretok_o200k",         // k_pto_scan1 / k_pto_scan2 / k_pto_mark: the split pattern's automaton + its two backward states
+    "k_pretok_o200k_docs",    // k_pto_scan1<true> / k_pto_mark<true>: the same bounded by the document flags
 };
 
 // ── context memory pool (common.h GbpePool) ───────────────────────────────

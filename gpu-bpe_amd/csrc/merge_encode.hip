@@ -735,12 +735,12 @@ struct MeDocJob {   // the documents of a batch call, n_docs > 0
 // the mode's mask of every document — of every piece between accepted specials — alone (mode NONE:
 // nothing) | the starts of the documents, of the specials and of the pieces after them;
 // ME_DOC_BIT = a document starts here; ME_SP_BIT / ME_SPIN_BIT = a special's first / other bytes.
-// The GPT-4 and cl100k rules see a piece alone through the document form of the pre-tokeniser: w.flags holds
+// The GPT-4, cl100k and o200k rules see a piece alone through the document form of the pre-tokeniser: w.flags holds
 // the document starts, then (k_sp_accept) the pieces' too.  The other modes' masks look one byte
 // back at most, so forcing a piece's first byte is all they need.  The first kernel checks the
 // offsets into the second word of w.back (zeroed by the caller).
 // the modes whose mask comes from a pre-tokeniser's kernels (pretok.hip)
-bool me_pretok(uint32_t mode) { return mode == GBPE_WORDS_GPT4 || mode == GBPE_WORDS_CL100K; }
+bool me_pretok(uint32_t mode) { return mode == GBPE_WORDS_GPT4 || mode == GBPE_WORDS_CL100K || mode == GBPE_WORDS_O200K; }
 
 int me_mask(gbpe_ctx* ctx, const uint8_t* d_in, uint64_t n, const uint8_t* d_ws, uint32_t mode, const MeDocJob* docs,
             const gbpe_specials* sp, const MeWork& w) {
@@ -757,6 +757,8 @@ int me_mask(gbpe_ctx* ctx, const uint8_t* d_in, uint64_t n, const uint8_t* d_ws,
         rc = gbpe_pretok_gpt4_docs_launch(ctx, d_in, n, w.flags, w.mask);
     } else if (mode == GBPE_WORDS_CL100K) {
         rc = gbpe_pretok_cl100k_launch(ctx, d_in, n, w.flags, w.mask);
+    } else if (mode == GBPE_WORDS_O200K) {
+        rc = gbpe_pretok_o200k_launch(ctx, d_in, n, w.flags, w.mask);
     } else if (mode == GBPE_WORDS_NONE) {
         GBPE_HIP(ctx, hipMemsetAsync(w.mask, 0, n, s));
     } else if (mode == GBPE_WORDS_MASK) {
@@ -814,6 +816,7 @@ int me_run(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, const char* wha
         GBPE_HIP(ctx, mask.reserve(ctx, n));
         rc = mode == GBPE_WORDS_GPT4     ? gbpe_pretok_gpt4_launch(ctx, d_in, n, mask.p)
              : mode == GBPE_WORDS_CL100K ? gbpe_pretok_cl100k_launch(ctx, d_in, n, nullptr, mask.p)
+             : mode == GBPE_WORDS_O200K  ? gbpe_pretok_o200k_launch(ctx, d_in, n, nullptr, mask.p)
                                          : gbpe_word_boundary_launch(ctx, d_in, n, mask.p);
         d_ws = mask.p;
     }
@@ -892,7 +895,8 @@ int me_run(gbpe_ctx* ctx, gbpe_bpe* bp, const gbpe_specials* sp, const char* wha
 }
 
 int me_words_check(gbpe_ctx* ctx, const void* word_starts, uint32_t mode) {
-    if (mode > GBPE_WORDS_CL100K) return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe encode: unknown words mode %u", mode);
+    if (mode > GBPE_WORDS_CL100K && mode != GBPE_WORDS_O200K)   // (5 is no mode: gpubpe.h)
+        return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe encode: unknown words mode %u", mode);
     if ((word_starts != nullptr) != (mode == GBPE_WORDS_MASK))
         return gbpe_set_error(ctx, GBPE_E_INVALID, "bpe encode: word_starts goes with GBPE_WORDS_MASK, and only with it");
     return GBPE_OK;

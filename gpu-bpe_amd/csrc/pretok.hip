@@ -19,6 +19,7 @@
 #include "common.h"
 #include "unicode_classes.h"
 #include "unicode_classes_cl100k.h"
+#include "unicode_classes_o200k.h"
 
 namespace {
 
@@ -539,8 +540,9 @@ __global__ __launch_bounds__(256) void k_doc_flags(const uint64_t* __restrict__ 
 }
 
 #include "pretok_cl100k.h"
+#include "pretok_o200k.h"
 
-enum PtRules { PT_GPT4 = 0, PT_CL100K = 1 };
+enum PtRules { PT_GPT4 = 0, PT_CL100K = 1, PT_O200K = 2 };
 
 struct UniTables {
     uint16_t* idx = nullptr;
@@ -550,15 +552,17 @@ struct UniTables {
 
 // the rules' class table on the context's device, uploaded on first use
 int uni_tables(gbpe_ctx* ctx, PtRules rules, const uint16_t** idx, const uint8_t** cls) {
-    static UniTables tabs[2][64];
+    static UniTables tabs[3][64];
     const int d = ctx->device;
     if (d < 0 || d >= 64) return gbpe_set_error(ctx, GBPE_E_INVALID, "device ordinal out of range");
     UniTables& t = tabs[rules][d];
     if (!t.idx) {
-        const bool cl = rules == PT_CL100K;
-        const void* hi = cl ? (const void*)kCl100kIndex : (const void*)kUniIndex;
-        const void* hc = cl ? (const void*)kCl100kClass : (const void*)kUniClass;
-        const size_t ni = cl ? sizeof(kCl100kIndex) : sizeof(kUniIndex), nc = cl ? sizeof(kCl100kClass) : sizeof(kUniClass);
+        const void* const his[3] = {kUniIndex, kCl100kIndex, kO200kIndex};
+        const void* const hcs[3] = {kUniClass, kCl100kClass, kO200kClass};
+        const size_t nis[3] = {sizeof(kUniIndex), sizeof(kCl100kIndex), sizeof(kO200kIndex)};
+        const size_t ncs[3] = {sizeof(kUniClass), sizeof(kCl100kClass), sizeof(kO200kClass)};
+        const void *hi = his[rules], *hc = hcs[rules];
+        const size_t ni = nis[rules], nc = ncs[rules];
         GBPE_HIP(ctx, dev_malloc(ctx, &t.idx, ni));
         GBPE_HIP(ctx, dev_malloc(ctx, &t.cls, nc));
         GBPE_HIP(ctx, hipMemcpy(t.idx, hi, ni, hipMemcpyHostToDevice));
@@ -580,9 +584,22 @@ int pretok_launch(gbpe_ctx* ctx, PtRules rules, const uint8_t* d_bytes, uint64_t
     if (rc != GBPE_OK) return rc;
     hipStream_t s = ctx->stream;
     const uint64_t nblk = gbpe_div_up(n, PT_BLK);
-    GBPE_HIP(ctx, ctx->pt_agg.reserve(ctx, (rules == PT_CL100K ? 2 : 1) * (nblk + 1) * sizeof(uint32_t)));
+    GBPE_HIP(ctx, ctx->pt_agg.reserve(ctx, (rules == PT_O200K ? 3 : rules == PT_CL100K ? 2 : 1) * (nblk + 1) * sizeof(uint32_t)));
     uint32_t* agg = (uint32_t*)ctx->pt_agg.p;
-    if (rules == PT_CL100K) {
+    if (rules == PT_O200K) {
+        uint64_t* fagg = (uint64_t*)ctx->pt_agg.p;        // the composed maps
+        uint32_t* bagg = (uint32_t*)(fagg + nblk + 1);    // the backward aggregates
+        const dim3 g((uint32_t)nblk), b(PT_TPB);
+        if (d_flags) hipLaunchKernelGGL(k_pto_scan1<true>, g, b, 0, s, d_bytes, n, d_flags, idx, cls, fagg, bagg);
+        else hipLaunchKernelGGL(k_pto_scan1<false>, g, b, 0, s, d_bytes, n, d_flags, idx, cls, fagg, bagg);
+        hipLaunchKernelGGL(k_pto_scan2, dim3(1), dim3(1024), 0, s, fagg, bagg, nblk);
+        if (d_flags)
+            hipLaunchKernelGGL(k_pto_mark<true>, g, b, 0, s, d_bytes, n, d_flags, idx, cls, (const uint64_t*)fagg,
+                               (const uint32_t*)bagg, d_ws);
+        else
+            hipLaunchKernelGGL(k_pto_mark<false>, g, b, 0, s, d_bytes, n, d_flags, idx, cls, (const uint64_t*)fagg,
+                               (const uint32_t*)bagg, d_ws);
+    } else if (rules == PT_CL100K) {
         uint32_t* bagg = agg + nblk + 1;   // the backward aggregates
         const dim3 g((uint32_t)nblk), b(PT_TPB);
         if (d_flags) hipLaunchKernelGGL(k_ptc_scan1<true>, g, b, 0, s, d_bytes, n, d_flags, idx, cls, agg, bagg);
@@ -624,6 +641,10 @@ int gbpe_pretok_cl100k_launch(gbpe_ctx* ctx, const uint8_t* d_bytes, uint64_t n,
     return pretok_launch(ctx, PT_CL100K, d_bytes, n, d_flags, d_ws);
 }
 
+int gbpe_pretok_o200k_launch(gbpe_ctx* ctx, const uint8_t* d_bytes, uint64_t n, const uint8_t* d_flags, uint8_t* d_ws) {
+    return pretok_launch(ctx, PT_O200K, d_bytes, n, d_flags, d_ws);
+}
+
 int gbpe_doc_flags_launch(gbpe_ctx* ctx, const uint64_t* d_doc_off, uint64_t n_docs, uint64_t n, uint8_t* d_flags,
                           uint32_t bit, uint32_t* d_invalid) {
     hipLaunchKernelGGL(k_doc_flags, dim3((uint32_t)gbpe_div_up(n_docs, 256)), dim3(256), 0, ctx->stream, d_doc_off, n_docs,
@@ -648,7 +669,7 @@ int gbpe_doc_offsets_error(gbpe_ctx* ctx, const char* what, uint32_t bad) {
                                                        : "do not end at the byte count");
 }
 
-// ── the entry points, each for both sets of rules ──────────────────────────
+// ── the entry points, each for every set of rules ──────────────────────────
 
 namespace {
 
@@ -763,4 +784,19 @@ extern "C" int gbpe_pretokenize_cl100k_batch_device(gbpe_ctx* ctx, const void* d
 extern "C" int gbpe_pretokenize_cl100k_batch(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, const uint64_t* doc_off,
                                              uint64_t n_docs, uint8_t* ws_out) {
     return pretok_batch_host(ctx, PT_CL100K, bytes, n, doc_off, n_docs, ws_out);
+}
+
+extern "C" int gbpe_pretokenize_o200k_device(gbpe_ctx* ctx, const void* d_bytes, uint64_t n, void* d_ws) {
+    return pretok_device(ctx, PT_O200K, d_bytes, n, d_ws);
+}
+extern "C" int gbpe_pretokenize_o200k(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, uint8_t* ws_out) {
+    return pretok_host(ctx, PT_O200K, bytes, n, ws_out);
+}
+extern "C" int gbpe_pretokenize_o200k_batch_device(gbpe_ctx* ctx, const void* d_bytes, uint64_t n, const void* d_doc_off,
+                                                   uint64_t n_docs, void* d_ws) {
+    return pretok_batch_device(ctx, PT_O200K, d_bytes, n, d_doc_off, n_docs, d_ws);
+}
+extern "C" int gbpe_pretokenize_o200k_batch(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, const uint64_t* doc_off,
+                                            uint64_t n_docs, uint8_t* ws_out) {
+    return pretok_batch_host(ctx, PT_O200K, bytes, n, doc_off, n_docs, ws_out);
 }

@@ -28,6 +28,7 @@ GBPE_TRAIN_TIMING = 1 << 1
 GBPE_TRAIN_GPT4_BOUNDARIES = 1 << 2
 
 GBPE_WORDS_NONE, GBPE_WORDS_MASK, GBPE_WORDS_HEURISTIC, GBPE_WORDS_GPT4, GBPE_WORDS_CL100K = 0, 1, 2, 3, 4
+GBPE_WORDS_O200K = 6   # (5 is no mode)
 GBPE_SPECIALS_MAX, GBPE_SPECIAL_MAX_BYTES = 254, 128
 GBPE_BPE_MAX_ID = 0xFFFFFF   # gbpe_bpe_upload_wide's bound; gbpe_bpe_upload's is 0xFFFF
 
@@ -170,6 +171,11 @@ _SIGS = [
     ("gbpe_pretokenize_cl100k_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_uint64, C.c_void_p]),
     ("gbpe_pretokenize_cl100k_batch_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                                        C.c_void_p]),
+    ("gbpe_pretokenize_o200k", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    ("gbpe_pretokenize_o200k_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    ("gbpe_pretokenize_o200k_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_uint64, C.c_void_p]),
+    ("gbpe_pretokenize_o200k_batch_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                      C.c_void_p]),
     ("gbpe_ctx_set_stream", C.c_int, [C.c_void_p, C.c_void_p]),
     ("gbpe_ctx_get_stream", C.c_void_p, [C.c_void_p]),
     ("gbpe_trainer_export_state", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_uint64, u64p,

@@ -22,7 +22,7 @@ import numpy as np
 from . import _lib
 
 WORDS_MODES = {"heuristic": _lib.GBPE_WORDS_HEURISTIC, "gpt4": _lib.GBPE_WORDS_GPT4,
-               "cl100k": _lib.GBPE_WORDS_CL100K}
+               "cl100k": _lib.GBPE_WORDS_CL100K, "o200k_base": _lib.GBPE_WORDS_O200K}
 
 
 def _bad_words(msg: str):
@@ -40,7 +40,7 @@ def checked_word_starts(n: int, word_starts=None, words=None):
         raise _bad_words("give word_starts or words, not both")
     if words is not None:
         if words not in WORDS_MODES:
-            raise _bad_words(f"words must be None, 'heuristic', 'gpt4' or 'cl100k', not {words!r}")
+            raise _bad_words(f"words must be None, 'heuristic', 'gpt4', 'cl100k' or 'o200k_base', not {words!r}")
         return WORDS_MODES[words], None
     if word_starts is None:
         return _lib.GBPE_WORDS_NONE, None
@@ -153,7 +153,7 @@ class MergeEncoder:
 
     def encode_bytes(self, data, word_starts=None, words=None, special=None) -> np.ndarray:
         """Tokens of ``data``.  ``word_starts`` (a mask, one entry per byte) or
-        ``words`` ('heuristic' / 'gpt4' / 'cl100k', the exact cl100k_base split: the
+        ``words`` ('heuristic' / 'gpt4' / 'cl100k', the exact cl100k_base split / 'o200k_base', the exact o200k_base split: the
         mask computed on the device) bound
         every token to one word; with neither the merges apply to the whole
         string.  An encoder with ``special_tokens`` gives each accepted special

@@ -10,7 +10,8 @@ accepts it like the reference trainer accepts its PreTokenizer (trainer.js:62-99
 
 ``rules="cl100k"`` on any of the calls gives the word starts of the cl100k_base
 split pattern instead (gbpe_pretokenize_cl100k); no normalisation
-belongs to it.
+belongs to it.  ``rules="o200k_base"`` gives those of the o200k_base split pattern
+(gbpe_pretokenize_o200k) in the same way.
 """
 from __future__ import annotations
 
@@ -21,13 +22,14 @@ import numpy as np
 from . import _lib
 
 
-RULES = ("gpt4", "cl100k")
+RULES = ("gpt4", "cl100k", "o200k_base")
+_SYMBOL = {"gpt4": "gpt4", "cl100k": "cl100k", "o200k_base": "o200k"}   # gbpe_pretokenize_<symbol>
 
 
 def _entry(rules: str, suffix: str = ""):
     if rules not in RULES:
-        raise ValueError(f"rules must be 'gpt4' or 'cl100k', not {rules!r}")
-    return getattr(_lib.load(), f"gbpe_pretokenize_{rules}{suffix}")
+        raise ValueError(f"rules must be 'gpt4', 'cl100k' or 'o200k_base', not {rules!r}")
+    return getattr(_lib.load(), f"gbpe_pretokenize_{_SYMBOL[rules]}{suffix}")
 
 
 class GpuPreTokenizer:
@@ -46,7 +48,7 @@ class GpuPreTokenizer:
 
     def pre_tokenize_batch(self, docs, offsets=None, rules: str = "gpt4"):
         """Word starts of many documents in one call (gbpe_pretokenize_gpt4_batch,
-        gbpe_pretokenize_cl100k_batch):
+        gbpe_pretokenize_cl100k_batch, gbpe_pretokenize_o200k_batch):
         returns ``(mask, offsets)`` over the concatenation, the mask of document d
         being ``mask[offsets[d]:offsets[d + 1]]`` — exactly ``pre_tokenize_bytes``
         of that document alone.  ``docs`` and ``offsets`` are ``flatten_documents``'s.

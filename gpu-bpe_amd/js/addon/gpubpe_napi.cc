@@ -21,6 +21,7 @@
 //   specialsUpload(ctx, bytes, offsets: Float64Array, ids: Uint32Array) -> external; specialsMark(ctx, specials, bytes, offsets | null) -> Uint8Array
 //   bpeEncodeSpecial(ctx, bpe, specials, bytes, wordStarts | null, mode) / bpeEncodeSpecialBatch(ctx, bpe, specials, bytes, offsets, wordStarts | null, mode)
 //   pretokenizeGpt4Batch(ctx, bytes, offsets: Float64Array) -> Uint8Array
+//   pretokenizeO200k(ctx, bytes) / pretokenizeO200kBatch(ctx, bytes, offsets) -> Uint8Array: the o200k_base split pattern's
 //   pretokenizeCl100k(ctx, bytes) / pretokenizeCl100kBatch(ctx, bytes, offsets) -> Uint8Array: the cl100k_base split
 //   vocabUpload(ctx, bytes: Uint8Array, offsets: Float64Array) -> vocab   vocabFree(vocab)
 //   decode(ctx, vocab, tokens: Uint32Array) -> Promise<Uint8Array>
@@ -289,9 +290,12 @@ napi_value WordBoundary(napi_env env, napi_callback_info info) {
 }
 
 // GPT-4 rule word starts (PreTokenizer.preTokenizeBytes, pre_tokenizer.mjs:459-509), or with
-// `cl100k` those of the cl100k_base split pattern (gbpe_pretokenize_cl100k)
-static napi_value pretokenize(napi_env env, napi_callback_info info, bool cl100k) {
-    const char* name = cl100k ? "pretokenizeCl100k" : "pretokenizeGpt4";
+// rules 1 those of the cl100k_base split pattern (gbpe_pretokenize_cl100k), 2 of o200k_base's (gbpe_pretokenize_o200k)
+static napi_value pretokenize(napi_env env, napi_callback_info info, int rules) {
+    static const char* const names[3] = {"pretokenizeGpt4", "pretokenizeCl100k", "pretokenizeO200k"};
+    static const char* const usage[3] = {"pretokenizeGpt4(ctx, Uint8Array)", "pretokenizeCl100k(ctx, Uint8Array)",
+                                         "pretokenizeO200k(ctx, Uint8Array)"};
+    const char* name = names[rules];
     size_t argc = 2;
     napi_value argv[2];
     NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
@@ -299,21 +303,23 @@ static napi_value pretokenize(napi_env env, napi_callback_info info, bool cl100k
     const uint8_t* data = nullptr;
     size_t len = 0;
     if (!ctx_usable(c) || argc < 2 || !get_bytes(env, argv[1], &data, &len)) {
-        napi_throw_type_error(env, nullptr, cl100k ? "pretokenizeCl100k(ctx, Uint8Array)" : "pretokenizeGpt4(ctx, Uint8Array)");
+        napi_throw_type_error(env, nullptr, usage[rules]);
         return nullptr;
     }
     napi_value ab, ta;
     void* dst = nullptr;
     NAPI_CALL(env, napi_create_arraybuffer(env, len, &dst, &ab));
     std::unique_lock<std::mutex> g(c->mu);
-    int rc = (cl100k ? gbpe_pretokenize_cl100k : gbpe_pretokenize_gpt4)(c->ctx, data, len, static_cast<uint8_t*>(dst));
+    int rc = (rules == 2 ? gbpe_pretokenize_o200k : rules == 1 ? gbpe_pretokenize_cl100k : gbpe_pretokenize_gpt4)(
+        c->ctx, data, len, static_cast<uint8_t*>(dst));
     g.unlock();
     if (rc != GBPE_OK) return throw_status(env, c->ctx, name, rc);
     NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, len, ab, 0, &ta));
     return ta;
 }
-napi_value PretokenizeGpt4(napi_env env, napi_callback_info info) { return pretokenize(env, info, false); }
-napi_value PretokenizeCl100k(napi_env env, napi_callback_info info) { return pretokenize(env, info, true); }
+napi_value PretokenizeGpt4(napi_env env, napi_callback_info info) { return pretokenize(env, info, 0); }
+napi_value PretokenizeCl100k(napi_env env, napi_callback_info info) { return pretokenize(env, info, 1); }
+napi_value PretokenizeO200k(napi_env env, napi_callback_info info) { return pretokenize(env, info, 2); }
 
 // ── trainer ──────────────────────────────────────────────────────────────
 
@@ -590,7 +596,7 @@ napi_value BpeEncode(napi_env env, napi_callback_info info) {
 }
 
 // bpeEncodeWords(ctx, bpe, bytes, wordStarts | null, mode): the merges inside each
-// word alone (gbpe_bpe_encode_words; mode = GBPE_WORDS_*: 1 takes the mask, 2, 3 and 4
+// word alone (gbpe_bpe_encode_words; mode = GBPE_WORDS_*: 1 takes the mask, 2, 3, 4 and 6
 // compute it on the device)
 // (`special`: bpeEncodeSpecial, the same with a special table after bpe — gbpe_bpe_encode_special)
 napi_value bpe_encode_words(napi_env env, napi_callback_info info, bool special) {
@@ -854,9 +860,15 @@ napi_value SpecialsMark(napi_env env, napi_callback_info info) {
 }
 
 // pretokenizeGpt4Batch(ctx, bytes, offsets) -> Uint8Array: each document's own GPT-4 word starts
-// (gbpe_pretokenize_gpt4_batch); pretokenizeCl100kBatch: its own cl100k_base ones (gbpe_pretokenize_cl100k_batch)
-static napi_value pretokenize_batch(napi_env env, napi_callback_info info, bool cl100k) {
-    const char* name = cl100k ? "pretokenizeCl100kBatch" : "pretokenizeGpt4Batch";
+// (gbpe_pretokenize_gpt4_batch); pretokenizeCl100kBatch: its own cl100k_base ones (gbpe_pretokenize_cl100k_batch);
+// pretokenizeO200kBatch: its own o200k_base ones (gbpe_pretokenize_o200k_batch)
+static napi_value pretokenize_batch(napi_env env, napi_callback_info info, int rules) {
+    static const char* const names[3] = {"pretokenizeGpt4Batch", "pretokenizeCl100kBatch", "pretokenizeO200kBatch"};
+    static const char* const usage[3] = {
+        "pretokenizeGpt4Batch(ctx, Uint8Array, offsets: Float64Array of non-negative integers)",
+        "pretokenizeCl100kBatch(ctx, Uint8Array, offsets: Float64Array of non-negative integers)",
+        "pretokenizeO200kBatch(ctx, Uint8Array, offsets: Float64Array of non-negative integers)"};
+    const char* name = names[rules];
     size_t argc = 3;
     napi_value argv[3];
     NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
@@ -865,24 +877,23 @@ static napi_value pretokenize_batch(napi_env env, napi_callback_info info, bool 
     size_t len = 0;
     std::vector<uint64_t> doc_off;
     if (!ctx_usable(c) || argc < 3 || !get_bytes(env, argv[1], &data, &len) || !get_doc_offsets(env, argv[2], &doc_off)) {
-        napi_throw_type_error(env, nullptr,
-                              cl100k ? "pretokenizeCl100kBatch(ctx, Uint8Array, offsets: Float64Array of non-negative integers)"
-                                     : "pretokenizeGpt4Batch(ctx, Uint8Array, offsets: Float64Array of non-negative integers)");
+        napi_throw_type_error(env, nullptr, usage[rules]);
         return nullptr;
     }
     napi_value ab, ta;
     void* dst = nullptr;
     NAPI_CALL(env, napi_create_arraybuffer(env, len, &dst, &ab));
     std::unique_lock<std::mutex> g(c->mu);
-    int rc = (cl100k ? gbpe_pretokenize_cl100k_batch : gbpe_pretokenize_gpt4_batch)(
+    int rc = (rules == 2 ? gbpe_pretokenize_o200k_batch : rules == 1 ? gbpe_pretokenize_cl100k_batch : gbpe_pretokenize_gpt4_batch)(
         c->ctx, data, len, doc_off.data(), doc_off.size() - 1, static_cast<uint8_t*>(dst));
     g.unlock();
     if (rc != GBPE_OK) return throw_status(env, c->ctx, name, rc);
     NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, len, ab, 0, &ta));
     return ta;
 }
-napi_value PretokenizeGpt4Batch(napi_env env, napi_callback_info info) { return pretokenize_batch(env, info, false); }
-napi_value PretokenizeCl100kBatch(napi_env env, napi_callback_info info) { return pretokenize_batch(env, info, true); }
+napi_value PretokenizeGpt4Batch(napi_env env, napi_callback_info info) { return pretokenize_batch(env, info, 0); }
+napi_value PretokenizeCl100kBatch(napi_env env, napi_callback_info info) { return pretokenize_batch(env, info, 1); }
+napi_value PretokenizeO200kBatch(napi_env env, napi_callback_info info) { return pretokenize_batch(env, info, 2); }
 
 struct EncodeWork {
     napi_async_work work = nullptr;
@@ -1288,6 +1299,8 @@ napi_value Init(napi_env env, napi_value exports) {
         {"pretokenizeGpt4Batch", nullptr, PretokenizeGpt4Batch, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"pretokenizeCl100k", nullptr, PretokenizeCl100k, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"pretokenizeCl100kBatch", nullptr, PretokenizeCl100kBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"pretokenizeO200k", nullptr, PretokenizeO200k, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"pretokenizeO200kBatch", nullptr, PretokenizeO200kBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"vocabUpload", nullptr, VocabUpload, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"vocabFree", nullptr, VocabFree, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"decode", nullptr, Decode, nullptr, nullptr, nullptr, napi_default, nullptr},

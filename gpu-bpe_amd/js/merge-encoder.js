@@ -4,8 +4,8 @@
  * with word starts, inside each word alone (pre-tokenise, then BPE per word).
  * encode(text) → { tokens, text, vocab, vocabStrings } as the reference's
  * (model = { vocab, vocabStrings, merges }).  opts = { wordStarts: Uint8Array (one
- * entry per byte, non-zero = word start) } or { words: 'gpt4' | 'heuristic' | 'cl100k' }
- * (the mask computed on the device; 'cl100k' is the exact cl100k_base split pattern);
+ * entry per byte, non-zero = word start) } or { words: 'gpt4' | 'heuristic' | 'cl100k' | 'o200k_base' }
+ * (the mask computed on the device; 'cl100k' / 'o200k_base' are the exact cl100k_base / o200k_base split patterns);
  * without opts no word is cut.  encodeBatch(docs,
  * opts) encodes many documents in one call.  new MergeEncoder(engine, model,
  * { specialTokens: { '<|endoftext|>': id, ... } | Map of string or Uint8Array to id })
@@ -25,7 +25,7 @@
 import { native } from './native.js';
 
 const WORDS_MASK = 1;
-const WORDS_MODES = { heuristic: 2, gpt4: 3, cl100k: 4 };
+const WORDS_MODES = { heuristic: 2, gpt4: 3, cl100k: 4, o200k_base: 6 };
 
 /** { bytes, offsets: Float64Array } of an array of Uint8Array laid end to end, or of one buffer with its offsets. */
 export function flattenDocuments(docs, offsets) {
@@ -128,7 +128,7 @@ export class MergeEncoder {
             return run(ws, WORDS_MASK);
         }
         if (!Object.prototype.hasOwnProperty.call(WORDS_MODES, words)) {
-            throw new TypeError("encodeBytes: words must be 'gpt4', 'heuristic' or 'cl100k'");
+            throw new TypeError("encodeBytes: words must be 'gpt4', 'heuristic', 'cl100k' or 'o200k_base'");
         }
         return run(null, WORDS_MODES[words]);
     }
@@ -154,7 +154,7 @@ export class MergeEncoder {
             mode = WORDS_MASK;
         } else if (words !== null) {
             if (!Object.prototype.hasOwnProperty.call(WORDS_MODES, words)) {
-                throw new TypeError("encodeBatch: words must be 'gpt4', 'heuristic' or 'cl100k'");
+                throw new TypeError("encodeBatch: words must be 'gpt4', 'heuristic', 'cl100k' or 'o200k_base'");
             }
             mode = WORDS_MODES[words];
         }
@@ -178,7 +178,7 @@ export class MergeEncoder {
         }
         if (words === null) return { mask: null, mode: 0 };
         if (!Object.prototype.hasOwnProperty.call(WORDS_MODES, words)) {
-            throw new TypeError(name + ": words must be 'gpt4', 'heuristic' or 'cl100k'");
+            throw new TypeError(name + ": words must be 'gpt4', 'heuristic', 'cl100k' or 'o200k_base'");
         }
         return { mask: null, mode: WORDS_MODES[words] };
     }

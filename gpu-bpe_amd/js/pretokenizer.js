@@ -6,8 +6,9 @@
  * the reference; BPETrainer.train(input, { preTokenizer }) accepts it the same
  * way (trainer.js:62-99).  Input must already be NFC (the reference
  * NFC-normalises first, which leaves NFC text unchanged).  Every call takes
- * { rules: 'cl100k' } for the word starts of the cl100k_base split pattern instead
- * (no normalisation belongs to it); the default, 'gpt4', is the rules above.
+ * { rules: 'cl100k' } for the word starts of the cl100k_base split pattern instead, or
+ * { rules: 'o200k_base' } for those of the o200k_base split pattern (no normalisation
+ * belongs to either); the default, 'gpt4', is the rules above.
  * Node 12 syntax.
  */
 import { native } from './native.js';
@@ -15,7 +16,9 @@ import { flattenDocuments } from './merge-encoder.js';
 
 function rulesOf(opts, what) {
     const rules = opts && opts.rules !== undefined && opts.rules !== null ? opts.rules : 'gpt4';
-    if (rules !== 'gpt4' && rules !== 'cl100k') throw new TypeError(what + ": rules must be 'gpt4' or 'cl100k'");
+    if (rules !== 'gpt4' && rules !== 'cl100k' && rules !== 'o200k_base') {
+        throw new TypeError(what + ": rules must be 'gpt4', 'cl100k' or 'o200k_base'");
+    }
     return rules;
 }
 
@@ -29,7 +32,8 @@ export class GpuPreTokenizer {
         const rules = rulesOf(opts, 'preTokenizeBytes');
         if (!rawBytes || rawBytes.length === 0) return { bytes: new Uint8Array(0), wordStarts: new Uint8Array(0) };
         const bytes = rawBytes instanceof Uint8Array ? rawBytes : new Uint8Array(rawBytes);
-        const wordStarts = rules === 'cl100k' ? native().pretokenizeCl100k(this._engine.device, bytes)
+        const wordStarts = rules === 'o200k_base' ? native().pretokenizeO200k(this._engine.device, bytes)
+            : rules === 'cl100k' ? native().pretokenizeCl100k(this._engine.device, bytes)
             : native().pretokenizeGpt4(this._engine.device, bytes);
         return { bytes, wordStarts };
     }
@@ -42,7 +46,8 @@ export class GpuPreTokenizer {
     preTokenizeBatch(docs, offsets, opts) {
         const rules = rulesOf(opts, 'preTokenizeBatch');
         const flat = flattenDocuments(docs, offsets);
-        const wordStarts = rules === 'cl100k' ? native().pretokenizeCl100kBatch(this._engine.device, flat.bytes, flat.offsets)
+        const wordStarts = rules === 'o200k_base' ? native().pretokenizeO200kBatch(this._engine.device, flat.bytes, flat.offsets)
+            : rules === 'cl100k' ? native().pretokenizeCl100kBatch(this._engine.device, flat.bytes, flat.offsets)
             : native().pretokenizeGpt4Batch(this._engine.device, flat.bytes, flat.offsets);
         return { bytes: flat.bytes, wordStarts: wordStarts, offsets: flat.offsets };
     }

@@ -134,6 +134,22 @@ int gbpe_pretokenize_cl100k_batch(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t 
 int gbpe_pretokenize_cl100k_batch_device(gbpe_ctx* ctx, const void* d_bytes, uint64_t n, const void* d_doc_off,
                                          uint64_t n_docs, void* d_ws);
 
+/* ── o200k_base word starts ──────────────────────────────────
+ * The same for the split pattern that o200k_base and its derivatives were trained
+ * with (tiktoken's, with Rust-regex meaning):
+ *   [^\r\n\p{L}\p{N}]?[\p{Lu}\p{Lt}\p{Lm}\p{Lo}\p{M}]*[\p{Ll}\p{Lm}\p{Lo}\p{M}]+(?i:'s|'t|'re|'ve|'m|'ll|'d)?
+ *   |[^\r\n\p{L}\p{N}]?[\p{Lu}\p{Lt}\p{Lm}\p{Lo}\p{M}]+[\p{Ll}\p{Lm}\p{Lo}\p{M}]*(?i:'s|'t|'re|'ve|'m|'ll|'d)?
+ *   |\p{N}{1,3}| ?[^\s\p{L}\p{N}]+[\r\n/]*|\s*[\r\n]+|\s+(?!\S)|\s+
+ * matched leftmost-first with backtracking (AXB is AX|B).  \s, [\r\n], the case
+ * folding, the apostrophe, the domain, the arguments, the batch layout and every
+ * status are gbpe_pretokenize_cl100k's; the classes are csrc/unicode_classes_o200k.h's. */
+int gbpe_pretokenize_o200k(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, uint8_t* ws_out);
+int gbpe_pretokenize_o200k_device(gbpe_ctx* ctx, const void* d_bytes, uint64_t n, void* d_ws);
+int gbpe_pretokenize_o200k_batch(gbpe_ctx* ctx, const uint8_t* bytes, uint64_t n, const uint64_t* doc_off,
+                                 uint64_t n_docs, uint8_t* ws_out);
+int gbpe_pretokenize_o200k_batch_device(gbpe_ctx* ctx, const void* d_bytes, uint64_t n, const void* d_doc_off,
+                                        uint64_t n_docs, void* d_ws);
+
 /* ── training (replaces trainer.js:149-335 BPETrainer.train over the
  *    train.wgsl kernels, training-pipeline.js:178-222 encodeBatch) ─────── */
 
@@ -431,6 +447,9 @@ int  gbpe_bpe_upload_wide(gbpe_ctx* ctx, const uint32_t* merges, uint32_t n_merg
 #define GBPE_WORDS_HEURISTIC  2u   /* gbpe_word_boundary's mask of the same bytes, computed on the device */
 #define GBPE_WORDS_GPT4       3u   /* gbpe_pretokenize_gpt4's mask of the same bytes (its domain), on the device */
 #define GBPE_WORDS_CL100K     4u   /* gbpe_pretokenize_cl100k's mask of the same bytes (its domain), on the device */
+#define GBPE_WORDS_O200K      6u   /* gbpe_pretokenize_o200k's mask of the same bytes (its domain), on the device.
+                                    * 5 is no mode and stays GBPE_E_INVALID (callers and tests pass it as their
+                                    * unknown mode); adding 6 leaves GBPE_ABI_VERSION as it is. */
 /* word_starts is non-NULL exactly when words_mode is GBPE_WORDS_MASK; anything
  * else, and an unknown mode, is GBPE_E_INVALID with nothing launched.  n == 0:
  * GBPE_OK, *n_out = 0, nothing launched.  On GBPE_E_CAPACITY *n_out holds the
@@ -453,8 +472,8 @@ int gbpe_bpe_encode_words_device(gbpe_ctx* ctx, gbpe_bpe* bpe, const void* d_byt
  * crosses a document start.  GBPE_WORDS_NONE: each document gets gbpe_bpe_encode's
  * tokens.  GBPE_WORDS_MASK: word_starts has n entries, one mask over the
  * concatenation; a document's first byte starts a word whatever it says.
- * GBPE_WORDS_HEURISTIC, GBPE_WORDS_GPT4, GBPE_WORDS_CL100K: each document's own mask
- * (gbpe_pretokenize_gpt4_batch's for GPT4, gbpe_pretokenize_cl100k_batch's for CL100K).  The mode and mask rules are
+ * GBPE_WORDS_HEURISTIC, GBPE_WORDS_GPT4, GBPE_WORDS_CL100K, GBPE_WORDS_O200K: each document's own mask
+ * (gbpe_pretokenize_gpt4_batch's for GPT4, gbpe_pretokenize_cl100k_batch's for CL100K, gbpe_pretokenize_o200k_batch's for O200K).  The mode and mask rules are
  * gbpe_bpe_encode_words's.  On GBPE_E_CAPACITY *n_out holds the required token
  * count, tok_off is complete, the first out_cap tokens are in place and nothing is
  * written at or beyond out[out_cap]; out == NULL with out_cap == 0 asks for the
@@ -516,8 +535,8 @@ int gbpe_specials_mark_device(gbpe_ctx* ctx, gbpe_specials* specials, const void
 /* gbpe_bpe_encode_words* with a special table.  The accepted specials cut a document
  * into pieces, the maximal runs of bytes outside every accepted special; the output
  * is, in order, what gbpe_bpe_encode_words returns for each piece ALONE in the
- * call's mode, and each special's id as one token.  GBPE_WORDS_GPT4, GBPE_WORDS_CL100K
- * and GBPE_WORDS_HEURISTIC: the word starts are those of the piece alone (not the whole
+ * call's mode, and each special's id as one token.  GBPE_WORDS_GPT4, GBPE_WORDS_CL100K,
+ * GBPE_WORDS_O200K and GBPE_WORDS_HEURISTIC: the word starts are those of the piece alone (not the whole
  * buffer's with the specials' edges forced: "it" EOT "'s" has word starts 1 1 in
  * its last piece).  GBPE_WORDS_MASK: the caller's mask restricted to the piece, its
  * first byte forced; the entries under a special's bytes are ignored.
